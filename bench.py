@@ -6,7 +6,7 @@ vocab 10003, 256 latents × 64 channels, 3 encoder layers × (1 cross + 6 self-a
 4/4/4 heads, dropout 0, batch 64 per GPU (reference README MLM command), AdamW + OneCycleLR,
 bf16 compute.  Synthetic token ids of that shape, random-init weights (no network on the GPU box).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...      (one rank per GPU, RCCL)
     python bench.py --config {mlm256,mlm64,seq_clf,seq_clf_ft,imagenet,long_mlm,mnist,lartpc} ...
 
@@ -19,6 +19,16 @@ latents; ``mnist`` = the 28×28 classifier of the README (batch 128); ``lartpc``
 segmentation experiment of ``run.py`` (512×512 synthetic events, batch 4, Adam + clip 10; the
 HIP backend runs it sparse — loss and gradients equal to the dense model's, see
 ``models/lartpc.py`` — and ``--backend reference`` densely, as the reference does).
+
+A plain run does only what its figure needs: set-up, ``--warmup`` untimed steps, ``--steps`` timed
+steps, the result line.  Every further measurement is asked for by an option of its own
+(``--config``, ``--backend``, ``--profile-steps``, ...); ``--full`` is where measurements that ride
+along with a run belong, and there are none today, so it changes nothing.  ``--dump-outputs DIR``
+writes what the last timed step produced as float32: the loss it returned (``loss.npy``), the
+parameters it left behind (``params.npy``, one flat vector) and the optimizer's first moment
+(``exp_avg.npy``).  With this option the last timed step starts from the run's initial, seeded
+state (``_TrainState``), so its results are the same from run to run up to the rounding of one
+step's atomic accumulation, and two builds can be compared output for output.
 
 Prints ONE JSON line on rank 0.  ``--backend reference`` measures the reference's own compute
 (nn.MultiheadAttention math, full-logit CE, torch AdamW) eagerly under bf16 autocast on the same
@@ -83,6 +93,10 @@ def parse(argv=None):
                     help="N > 1: AdamW per bucket right behind its all-reduce (on; auto = with --overlap on) or one "
                          "pass after all (off)")
     ap.add_argument("--dense", action="store_true", help="lartpc: evaluate all pixels (the reference's cost)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's outputs to DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline figure (none today: same as a plain run)")
     ap.add_argument("--profile-steps", type=int, default=0)
     ap.add_argument("--profile-stacks", type=int, default=0,
                     help="with --profile-steps: list the framework (aten) ops that touch device tensors in the "
@@ -132,6 +146,91 @@ def _aten_stacks(engine, data, steps, depth):
         print(f"{op} x{n}", file=sys.stderr)
         for fr in frames:
             print(f"    {fr}", file=sys.stderr)
+
+
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs writes at most this much in all
+
+
+class _TrainState:
+    """The state a step reads and writes besides its batch: trained parameters (with their bf16
+    shadow), optimizer moments and step count, learning-rate schedule, masking and dropout RNG.
+    ``--dump-outputs`` records it before the first warm-up step and puts it back before the last
+    timed step, so what that step computes depends on the run's seeded inputs alone.  (The kernels
+    accumulate weight gradients with fp32 atomics; bf16 training turns that order-dependent
+    rounding into parameter differences of 1e-3 within 25 steps, so the state a run has reached
+    after its earlier steps is not the same from run to run.)"""
+
+    def __init__(self, params, opt, sched, engine, device, masking):
+        import copy
+
+        import torch
+
+        from perceiver_io_amd.ops import masking as M
+
+        self.params, self.opt, self.sched, self.engine, self.device = params, opt, sched, engine, device
+        self.fused = hasattr(opt, "flat")
+        if masking:  # created here as the first step would (same draw from the seeded default generator)
+            M.mask_state(device)
+        self.mask = {d: st.clone() for d, st in M._states.items()}
+        if self.fused:
+            bufs = [opt.flat.data, opt.flat.shadow, opt.exp_avg, opt.exp_avg_sq]
+            self.bufs = [(b, b.clone()) for b in bufs if b is not None]
+            self.step = opt._step
+        else:
+            self.bufs = [(p.data, p.detach().clone()) for p in params]
+            self.opt_state = copy.deepcopy(opt.state_dict())
+        self.lrs = [g["lr"] for g in opt.param_groups]
+        self.sched_state = copy.deepcopy(sched.state_dict()) if sched is not None else None
+        self.cpu_rng = torch.get_rng_state()
+        self.gpu_rng = torch.cuda.get_rng_state(device) if device.type == "cuda" else None
+
+    def restore(self):
+        import copy
+
+        import torch
+
+        from perceiver_io_amd.ops import masking as M
+
+        with torch.no_grad():
+            for dst, src in self.bufs:
+                dst.copy_(src)
+            for d, st in self.mask.items():
+                M._states[d].copy_(st)
+        if self.fused:
+            self.opt._step = self.step
+        else:
+            self.opt.load_state_dict(copy.deepcopy(self.opt_state))
+        if self.sched is not None:
+            self.sched.load_state_dict(copy.deepcopy(self.sched_state))
+        for g, lr in zip(self.opt.param_groups, self.lrs):
+            g["lr"] = lr
+        self.engine._seed_rng = None  # the captured steps' dropout seeds: restarts from torch's seed
+        torch.set_rng_state(self.cpu_rng)
+        if self.gpu_rng is not None:
+            torch.cuda.set_rng_state(self.gpu_rng, self.device)
+
+
+def _dump_outputs(path, loss, params, opt):
+    """The last timed step's results as float32 ``.npy`` files: the loss it returned, the parameters
+    it updated and the optimizer's first moment (0.1 x that step's gradient), each a fixed, seeded
+    sample where the three would exceed the size cap."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    if hasattr(opt, "flat"):
+        arrays = {"params": opt.flat.data, "exp_avg": opt.exp_avg}
+    else:
+        moments = [opt.state[p]["exp_avg"] if "exp_avg" in opt.state.get(p, {}) else torch.zeros_like(p) for p in params]
+        arrays = {"params": torch.cat([p.detach().float().reshape(-1) for p in params]),
+                  "exp_avg": torch.cat([m.detach().float().reshape(-1) for m in moments])}
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
+    cap = (DUMP_MAX_BYTES - (1 << 20)) // 4 // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > cap:
+            a = a[np.sort(np.random.RandomState(0).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def _opt(lr=3e-3, wd=0.0):
@@ -368,6 +467,9 @@ def main(argv=None):
         return tuple(t.to(device) for t in b)
 
     data = [to_dev(make_batch(g)) for _ in range(4)]
+    state0 = None
+    if args.dump_outputs:
+        state0 = _TrainState(params, opt, sched, engine, device, masking=args.config in ("mlm256", "mlm64", "long_mlm"))
     for i in range(args.warmup):
         loss = engine.step(data[i % 4], ring_view=True)
     if cuda:
@@ -377,6 +479,8 @@ def main(argv=None):
         torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.steps):
+        if state0 is not None and i == args.steps - 1:
+            state0.restore()
         loss = engine.step(data[i % 4], ring_view=True)
     if cuda:
         torch.cuda.synchronize()
@@ -392,6 +496,8 @@ def main(argv=None):
     from perceiver_io_amd.parallel.reducer import params_in_sync
 
     sync_diff = params_in_sync(reducer.flat if reducer is not None else params) if world > 1 else 0.0
+    if args.dump_outputs and info.is_main:
+        _dump_outputs(args.dump_outputs, loss, params, opt)
     if args.profile_steps and cuda:
         from torch.profiler import ProfilerActivity, profile
 

@@ -10,7 +10,10 @@ import torch
 from perceiver_io_amd.ops import emulation
 from perceiver_io_amd.ops import fused as F
 
-REF_TOKENIZER = "/root/reference/.cache/imdb-tokenizer-10003.json"
+# the reference's shipped tokenizer (its ``.cache/imdb-tokenizer-10003.json``), carried in the package
+REF_TOKENIZER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "perceiver_io_amd", "data",
+                             "assets", "imdb-tokenizer-10003.json")
+REF_TOKENIZER_SHA256 = "fb7413fe1ab8a27da582c6578ff8c2eb7dcf73096496b5da8f6e6a8881408d54"  # of the reference's file
 
 
 def test_lartpc_run_cpu_smoke(tmp_path):
@@ -69,7 +72,6 @@ def test_tokenizer_train_save_load_roundtrip(tmp_path):
     assert tok2.decode(ids) == "the movie was great"
 
 
-@pytest.mark.skipif(not os.path.exists(REF_TOKENIZER), reason="reference tokenizer JSON not mounted")
 def test_reference_tokenizer_json_loads():
     """The tokenizer shipped in the reference tree (SURVEY #37) loads with the JSON loader."""
     from perceiver_io_amd.utils.tokenizer import load_tokenizer
@@ -123,7 +125,6 @@ def _fake_imdb(root, n=3):
                 (d / f"{i}_1.txt").write_text(f"this movie was {'bad' if lab == 'neg' else 'great'}<br />film {i}")
 
 
-@pytest.mark.skipif(not os.path.exists(REF_TOKENIZER), reason="reference tokenizer not mounted")
 @pytest.mark.parametrize("explicit", [False, True])
 def test_imdb_uses_shipped_tokenizer(tmp_path, explicit):
     """The reference's shipped tokenizer (``.cache/imdb-tokenizer-10003.json``) is loaded as is —
@@ -241,6 +242,7 @@ def test_shipped_reference_tokenizer_installed_for_real_data(tmp_path):
     """A real-data IMDB run at vocab 10003 without a tokenizer in data_dir installs the shipped
     reference vocabulary (reference .cache/imdb-tokenizer-10003.json) instead of training one."""
     import filecmp
+    import hashlib
     import os
 
     from perceiver_io_amd.data.imdb import IMDBDataModule, shipped_tokenizer
@@ -259,8 +261,7 @@ def test_shipped_reference_tokenizer_installed_for_real_data(tmp_path):
     tok = dm.tokenizer
     assert tok.get_vocab_size() == 10003
     assert [tok.token_to_id(t) for t in (PAD_TOKEN, UNK_TOKEN, MASK_TOKEN)] == [0, 1, 2]
-    ref = "/root/reference/.cache/imdb-tokenizer-10003.json"
-    if os.path.exists(ref):  # byte-identical to the reference's shipped file
-        assert filecmp.cmp(ref, shipped_tokenizer(10003), shallow=False)
+    # byte-identical to the reference's shipped file
+    assert hashlib.sha256(open(shipped_tokenizer(10003), "rb").read()).hexdigest() == REF_TOKENIZER_SHA256
     ids = tok.encode("i have watched this [MASK] and it was awesome").ids
     assert 2 in ids and 1 not in ids

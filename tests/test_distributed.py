@@ -127,6 +127,7 @@ def test_bench_self_spawns_ranks_cpu_dry_run():
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    env.update(CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")  # the dry run, also on a machine with one GPU
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
                         "--batch", "2", "--seq-len", "32", "--latents", "16", "--channels", "32", "--vocab", "300"],
                        capture_output=True, text=True, env=env, timeout=600, cwd=root)

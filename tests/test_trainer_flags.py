@@ -123,6 +123,41 @@ def test_bench_json_contract_cpu():
     assert rec["config"]["global_batch"] == 2 and rec["config"]["seq_len"] == 32
 
 
+def test_bench_dump_outputs_cpu(tmp_path):
+    """``--dump-outputs DIR`` writes the last timed step's loss, the parameters it updated and the
+    optimizer's first moment as float32 ``.npy`` files.  Weights, data and masking are seeded and
+    the last timed step starts from the run's initial state, so a second run writes the same
+    arrays, also after another number of steps that ends on the same batch (3 and 7 of 4 batches).
+    ``--full`` is accepted and leaves the result line's fields as they are."""
+    import numpy as np
+
+    env = dict(os.environ, CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")
+    recs, dumps = [], []
+    for name, steps, extra in (("a", 3, []), ("b", 7, ["--full"])):
+        d = tmp_path / name
+        out = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--backend", "torch", "--dtype", "fp32",
+                              "--batch", "2", "--seq-len", "32", "--latents", "8", "--vocab", "64", "--steps", str(steps),
+                              "--warmup", "1", "--dump-outputs", str(d)] + extra,
+                             cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, out.stderr[-2000:]
+        assert [l for l in out.stdout.splitlines() if l.strip() and not l.startswith("{")] == []
+        recs.append(json.loads(out.stdout.strip()))
+        assert sorted(os.listdir(d)) == ["exp_avg.npy", "loss.npy", "params.npy"]
+        dumps.append({f[:-4]: np.load(d / f) for f in os.listdir(d)})
+    for rec, steps, dump in zip(recs, (3, 7), dumps):
+        assert rec["steps"] == steps and rec["ms_per_step"] > 0
+        assert abs(rec["value"] - 2 * 1e3 / rec["ms_per_step"]) <= 0.01 * rec["value"]  # samples/s of a timed step
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in dump.values())
+        assert dump["loss"].shape == (1,) and abs(float(dump["loss"][0]) - rec["final_loss"]) <= 1e-4
+        assert dump["params"].ndim == 1 and dump["params"].size > 64 * 8
+        assert dump["exp_avg"].shape == dump["params"].shape and np.abs(dump["exp_avg"]).max() > 0
+        assert sum(a.nbytes for a in dump.values()) <= 64 << 20
+    assert set(recs[0]) == set(recs[1])
+    assert np.array_equal(dumps[0]["loss"], dumps[1]["loss"])
+    assert np.array_equal(dumps[0]["params"], dumps[1]["params"])
+    assert np.array_equal(dumps[0]["exp_avg"], dumps[1]["exp_avg"])
+
+
 def test_allreduce_dtype_flag(tmp_path):
     """--trainer.allreduce_dtype (the gradient all-reduce wire format, SURVEY C-03) reaches the trainer;
     a bad value is rejected.  The bf16 wire itself is exercised on 2 gloo ranks in

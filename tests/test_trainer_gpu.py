@@ -1,7 +1,7 @@
 """Trainer + CLI on the GPU: fused bf16 path, hipGraph-captured steps, checkpoint round trip.
 
 The entrypoints run with the reference's DEFAULT data behaviour: the IMDB collator pads each
-batch to its longest sequence (``/root/reference/data/imdb.py:52-63``) and the loaders keep
+batch to its longest sequence (reference ``data/imdb.py:52-63``) and the loaders keep
 the partial last batch (``:112-126``; pl_bolts MNIST likewise) — the step engine caches one
 captured graph per (bucketed) batch shape.
 """

@@ -117,9 +117,11 @@ def test_mlm_then_frozen_seq_clf_transfer_and_resume(tmp_path):
     assert all(torch.equal(best["model.encoder." + k].cpu(), v.cpu()) for k, v in enc_clf.items())  # frozen + transferred
     assert not any(p.requires_grad for p in clf.model.model.encoder.parameters())
     ck2 = [c for c in clf.trainer.callbacks if type(c).__name__ == "ModelCheckpoint"][0]
-    # resume: continues from the stored global step
+    # resume (the run's own configuration: the checkpoint's optimizer state covers the trained
+    # parameters, which with a GPU present are the unfrozen ones only): continues from the stored
+    # global step
     res = run_cli("seq_clf", tmp_path, "fit", *common, f"--trainer.resume_from_checkpoint={ck2.best_model_path}",
-                  "--trainer.max_epochs=2", "--trainer.limit_train_batches=2")
+                  "--model.freeze_encoder=true", "--trainer.max_epochs=2", "--trainer.limit_train_batches=2")
     assert res.trainer.global_step == clf.trainer.global_step + 2
 
 
