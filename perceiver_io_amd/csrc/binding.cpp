@@ -111,6 +111,10 @@ void ce2_bwd_launch(const uint16_t*, const int64_t*, const uint16_t*, const floa
                     const int64_t*, hipStream_t);
 int ce_num_splits(int, int);
 int ce_dw_splits(int, int);
+int vocab_topk_splits(int, int);
+int vocab_topk_kt(int);
+void vocab_topk_launch(int, const float*, const int64_t*, long long, const uint16_t*, const float*, int, int, int, int,
+                       float*, int*, float2*, float*, int64_t*, float*, hipStream_t);
 void mlm_select_launch(const int64_t*, int, int, int, int, int64_t*, int64_t*, int*, int64_t*, int64_t*, float*, bool*, bool*,
                        const float*, int, float*, hipStream_t);
 void ce_bwd_launch(int, const uint16_t*, const int64_t*, const uint16_t*, const float*, const float*, const float*,
@@ -120,6 +124,7 @@ void embed_fwd_launch(const int64_t*, const float*, const float*, float*, long l
 unsigned check_errors_elementwise(bool);
 unsigned check_errors_mlm_head(bool);
 unsigned check_errors_ce_head(bool);
+unsigned check_errors_topk_head(bool);
 unsigned check_errors_rowgemm(bool);
 void embed_bwd_launch(const int64_t*, const float*, float*, float*, int, int, int, float, hipStream_t);
 void embed_bwd_sorted_launch(const int64_t*, const int64_t*, const float*, float*, long long, int, float, hipStream_t);
@@ -176,7 +181,8 @@ hipStream_t stream() { return at::hip::getCurrentHIPStream(); }
 // outside [0, V) ∪ {-100}); reset clears them
 int64_t check_errors(bool reset) {
   return (int64_t)(pio::check_errors_elementwise(reset) | pio::check_errors_mlm_head(reset) |
-                   pio::check_errors_ce_head(reset) | pio::check_errors_rowgemm(reset));
+                   pio::check_errors_ce_head(reset) | pio::check_errors_topk_head(reset) |
+                   pio::check_errors_rowgemm(reset));
 }
 bool checked_build() { return PIO_CHECKS != 0; }
 // checked builds, outside graph capture: wait for the kernel just launched and raise on any
@@ -1328,6 +1334,43 @@ OptT ce_bwd(Tensor h, Tensor labels, Tensor w, Tensor bias, Tensor lse, Tensor g
   return c10::nullopt;
 }
 
+// the k largest logits of each row of h·wᵀ + bias (row r = h[idx[r]] when idx is given, else h[r]),
+// their vocabulary indices and the row's log-sum-exp over the vocabulary: → {values (M, k) fp32,
+// sorted descending (the lower index first on exact ties), indices (M, k) int64, lse (M,)}.  The
+// logits live in MFMA tiles only (topk_head.hip); C ∈ {64, 128}, 1 ≤ k ≤ 8, k ≤ V.
+std::vector<Tensor> vocab_topk(Tensor h, OptT idx, Tensor w, Tensor bias, int64_t k) {
+  CHECK_DT(h, torch::kFloat32);
+  TORCH_CHECK(h.dim() == 2 && w.dim() == 2 && bias.dim() == 1, "vocab_topk: h (R, C), w (V, C), bias (V,)");
+  TORCH_CHECK(h.is_contiguous() && w.is_contiguous() && bias.is_contiguous(), "vocab_topk: operands must be contiguous");
+  const int C = (int)h.size(1), V = (int)w.size(0);
+  TORCH_CHECK(w.size(1) == C && bias.size(0) == V && (C == 64 || C == 128), "vocab_topk: bad vocab head shape");
+  TORCH_CHECK(k >= 1 && k <= 8 && k <= V, "vocab_topk: k must be in [1, min(8, V)]");
+  TORCH_CHECK(w.get_device() == h.get_device() && bias.get_device() == h.get_device(), "vocab_topk: operands on one device");
+  const int64_t M64 = idx.has_value() ? idx->numel() : h.size(0);
+  TORCH_CHECK(M64 < (int64_t)1 << 24, "vocab_topk: too many rows");
+  const int M = (int)M64;
+  const int64_t* ip = nullptr;
+  if (idx.has_value()) {
+    CHECK_DT(*idx, torch::kInt64);
+    TORCH_CHECK(idx->is_contiguous() && idx->get_device() == h.get_device(),
+                "vocab_topk: idx must be a contiguous int64 tensor on the rows' device");
+    ip = idx->data_ptr<int64_t>();
+  }
+  auto f32 = h.options().dtype(torch::kFloat32);
+  Tensor values = torch::empty({M, k}, f32), indices = torch::empty({M, k}, f32.dtype(torch::kInt64));
+  Tensor lse = torch::empty({M}, f32);
+  if (M == 0) return {values, indices, lse};
+  TORCH_CHECK(h.size(0) >= 1, "vocab_topk: no rows to gather from");
+  const int ns = pio::vocab_topk_splits(M, V), kt = pio::vocab_topk_kt((int)k);
+  Tensor cv = torch::empty({ns, M, kt}, f32), ci = torch::empty({ns, M, kt}, f32.dtype(torch::kInt32));
+  Tensor pml = torch::empty({ns, M, 2}, f32);
+  pio::vocab_topk_launch(C, h.data_ptr<float>(), ip, h.size(0), bfp(w), f32p(bias), M, V, (int)k, ns, cv.data_ptr<float>(),
+                         ci.data_ptr<int>(), reinterpret_cast<float2*>(pml.data_ptr<float>()), values.data_ptr<float>(),
+                         indices.data_ptr<int64_t>(), lse.data_ptr<float>(), stream());
+  checked_sync("vocab_topk");
+  return {values, indices, lse};
+}
+
 Tensor embed_fwd(Tensor ids, Tensor E, Tensor P, double scale) {
   TORCH_CHECK(ids.is_contiguous() && E.is_contiguous() && P.is_contiguous());
   CHECK_DT(ids, torch::kInt64);
@@ -1982,6 +2025,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("lse"), py::arg("gout"), py::arg("count"), py::arg("dH"), py::arg("dW"), py::arg("db"),
         py::arg("accumulate"), py::arg("rowmap") = py::none(), py::arg("slab") = false, py::arg("u") = py::none(),
         py::arg("u_ml") = py::none());
+  m.def("vocab_topk", &vocab_topk, py::arg("h"), py::arg("idx"), py::arg("w"), py::arg("bias"), py::arg("k"));
   m.def("embed_fwd", &embed_fwd);
   m.def("embed_bwd", &embed_bwd, py::arg("ids"), py::arg("g"), py::arg("dE"), py::arg("dP"), py::arg("scale"),
         py::arg("job_slab") = py::none(), py::arg("job_dsts") = std::vector<Tensor>(),

@@ -170,6 +170,18 @@ class PerceiverIO(Sequential):
         finally:
             look["want_kv"] = look["have_q"] = None
 
+    @torch.no_grad()
+    def predict_topk(self, x, pad_mask=None, k: int = 1):
+        """The ``k`` most likely classes of a one-query classification decoder without a logits
+        tensor: ``(values (B, k), indices (B, k), lse (B,))``; ``indices[:, 0]`` is the argmax class
+        and ``values - lse[:, None]`` the log-probabilities.  No dropout runs under ``eval()``."""
+        lin = getattr(self.decoder.output_adapter, "linear", None)
+        if not isinstance(lin, nn.Linear) or self.decoder.output.shape[0] != 1:
+            raise ValueError("predict_topk needs a one-query decoder whose output adapter has a `linear` head")
+        x_latent, _ = self.encoder(x, pad_mask)
+        h = self.decoder.hidden(x_latent)  # (B, 1, C)
+        return ops.mlm_head.vocab_topk(h.reshape(h.shape[0], -1), lin.weight, lin.bias, k)
+
     @property
     def encoder(self) -> PerceiverEncoder:
         return self[0]
@@ -239,6 +251,36 @@ class PerceiverMLM(nn.Module):
         x_latent, _ = self.encoder(x_masked, pad_mask)
         x_logits = self.decoder.output_adapter(self.decoder.hidden(x_latent, num_queries=l))
         return x_logits, x_labels
+
+    @torch.no_grad()
+    def predict_topk(self, x_input, pad_mask=None, k: int = 5, positions=None):
+        """The ``k`` most likely tokens at chosen positions without the ``(B, L, V)`` logits.
+
+        ``positions``: bool ``(B, L)``, default the ``[MASK]`` tokens of ``x_input``.  No masking
+        is applied; call under ``eval()``.  Only the requested positions are decoded (decoder
+        queries never interact) and projected onto the vocabulary.  Returns ``(where, values,
+        indices, lse)``: ``where`` int64 ``(S, 2)`` holds (sample, position) in row-major order of
+        ``positions``; ``values`` / ``indices`` ``(S, k)`` are the logits sorted descending (lower
+        token id first on exact ties on the fused path) and their token ids, ``lse`` ``(S,)`` the
+        log-sum-exp over the vocabulary.  One host sync sizes ``S``."""
+        if positions is None:
+            positions = x_input == self.masking.mask_token_id
+        positions = positions.to(torch.bool)
+        where = positions.nonzero()
+        dev = x_input.device
+        if where.shape[0] == 0:
+            return (where, torch.empty(0, k, device=dev), torch.empty(0, k, dtype=torch.int64, device=dev),
+                    torch.empty(0, device=dev))
+        # per-sequence slots padded to the largest count; unused slots decode distinct positions
+        cap = int(torch.bincount(where[:, 0]).max())
+        labels = torch.where(positions, 0, -100)
+        idx, labels_c, _ = ops.mlm_head.compact_per_row(labels, cap)
+        x_latent, _ = self.encoder(x_input, pad_mask)
+        h = self.decoder.hidden_at(x_latent, idx)  # (B, cap, C)
+        real = (labels_c.reshape(-1) != -100).nonzero().squeeze(1)  # slots in the order of ``where``
+        lin = self.decoder.output_adapter.linear
+        values, indices, lse = ops.mlm_head.vocab_topk(h, lin.weight, lin.bias, k, idx=real)
+        return where, values, indices, lse
 
     def loss(self, x_input, pad_mask=None, labels=None, x_masked=None):
         """Masked-token cross-entropy (mean over selected positions) without

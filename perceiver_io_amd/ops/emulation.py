@@ -562,6 +562,17 @@ def ce_fwd(h, idx, labels, w, bias, count, zero_out=None, count_labels=False):
     return loss.sum() / count.reshape(()).clamp(min=1), lse, _ce_rows(h, idx).to(torch.bfloat16).contiguous()
 
 
+def vocab_topk(h, idx, w, bias, k):
+    """→ (values (M, k) fp32 sorted descending, indices (M, k) int64, lse (M,)) of the rows'
+    logits ``_bf(h_rows) @ _bf(w).T + bias``; on exact ties the lower vocabulary index comes first
+    (a stable descending sort).  Rows of ``h`` are gathered through ``idx`` when given."""
+    logits = _bf(_ce_rows(h, idx).float()) @ _bf(w.float()).t() + bias.float()
+    if not 1 <= k <= logits.shape[1]:
+        raise ValueError(f"vocab_topk: k must be in [1, {logits.shape[1]}], got {k}")
+    values, indices = torch.sort(logits, dim=-1, descending=True, stable=True)
+    return values[:, :k].contiguous(), indices[:, :k].contiguous(), torch.logsumexp(logits, -1)
+
+
 def ce_bwd(h, labels, w, bias, lse, gout, count, dH, dW, db, accumulate, rowmap=None, slab=False, u=None, u_ml=None):
     """h: the compact bf16 rows returned by ce_fwd.  slab=True: dW | db are returned as a one-row
     (1, V·C + V₄) slab instead of being added.  ``u`` / ``u_ml`` (the HIP two-pass head's forward

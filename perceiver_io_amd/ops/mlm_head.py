@@ -217,6 +217,49 @@ def compact_lm_loss(h: torch.Tensor, labels_c: torch.Tensor, count: torch.Tensor
     return F.cross_entropy(logits.float(), lab, ignore_index=-100, reduction="sum") / count.clamp(min=1)
 
 
+# ------------------------------------------------------------------------------------------
+# prediction: the k best vocabulary entries of chosen rows, no logits tensor
+# ------------------------------------------------------------------------------------------
+TOPK_MAX_K = 8  # the head kernel's running top-k is compiled for Kt ∈ {1, 4, 8}
+
+
+@torch.no_grad()
+def vocab_topk(h: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, k: int, idx: torch.Tensor = None):
+    """The ``k`` largest logits of ``F.linear(rows, weight, bias)``, their vocabulary indices
+    and the rows' log-sum-exp over the whole vocabulary: ``(values (M, k), indices (M, k) int64,
+    lse (M,))``, so ``log_probs = values - lse[:, None]``.  ``rows`` are the rows of ``h``
+    (``(..., C)``, flattened) — those at ``idx`` (int64 ``(M,)``) when given.
+
+    HIP path (C ∈ {64, 128}, k ≤ 8): ``csrc/topk_head.hip`` over the bf16 weight shadow; the
+    logits exist only as MFMA tiles, and exact ties come lower index first.  Anything else
+    (CPU, the eager backends, C = 32, k > 8) is ``F.linear`` in the tensor's own precision on the
+    selected rows + ``topk`` + ``logsumexp``."""
+    from . import use_hip
+
+    c = h.shape[-1]
+    h2 = h.reshape(-1, c)
+    v = weight.shape[0]
+    if not 1 <= k <= v:
+        raise ValueError(f"vocab_topk: k must be in [1, {v}], got {k}")
+    if use_hip(h) and c in (64, 128) and k <= TOPK_MAX_K:
+        from .fused import weight_cache
+
+        if h2.dtype != torch.float32 or not h2.is_contiguous():
+            h2 = h2.float().contiguous()
+        if idx is not None and (idx.dtype != torch.int64 or not idx.is_contiguous()):
+            idx = idx.to(torch.int64).contiguous()
+        # a head without a bias: the logit accumulators start at zero
+        b = bias.detach() if bias is not None else torch.zeros(v, device=h2.device, dtype=torch.float32)
+        if b.dtype != torch.float32 or not b.is_contiguous():
+            b = b.float().contiguous()
+        values, indices, lse = ext.vocab_topk(h2, idx, weight_cache.get(weight), b, int(k))
+        return values, indices, lse
+    rows = h2 if idx is None else h2.index_select(0, idx)
+    logits = F.linear(rows, weight, bias).float()
+    values, indices = logits.topk(k, dim=-1)
+    return values, indices, torch.logsumexp(logits, -1)
+
+
 def _index_add_grad(p: torch.nn.Parameter, idx: torch.Tensor, g: torch.Tensor):
     """``p.grad[idx] += g`` straight into the (flat-buffer) gradient: one kernel, no autograd
     zeros + index_add + AccumulateGrad."""
