@@ -150,6 +150,11 @@ void pixel_ce_fwd_launch(int, int, const float*, const float*, const float*, con
                          float*, float*, float*, hipStream_t);
 void pixel_ce_bwd_launch(int, int, const float*, const float*, const float*, const int64_t*, const float*,
                          const float*, const float*, long long, float*, float*, float*, float*, hipStream_t);
+void pixel_predict_launch(int, int, const float*, const float*, const float*, const int64_t*, const bool*, const int64_t*,
+                          long long, long long, long long, uint8_t*, float*, uint8_t*, int*, hipStream_t);
+void nonzero_compact_launch(const float*, int, long long, long long, int, int, int*, float*, int64_t*, bool*, int*,
+                            hipStream_t);
+unsigned check_errors_pixel_head(bool);
 void adamw_launch(float*, float*, float*, float*, uint16_t*, long long, const float*, float, float, float, float,
                   int, int, const float*, float*, int, const float*, hipStream_t);
 void cast_bf16_launch(const float*, uint16_t*, long long, hipStream_t);
@@ -182,7 +187,7 @@ hipStream_t stream() { return at::hip::getCurrentHIPStream(); }
 int64_t check_errors(bool reset) {
   return (int64_t)(pio::check_errors_elementwise(reset) | pio::check_errors_mlm_head(reset) |
                    pio::check_errors_ce_head(reset) | pio::check_errors_topk_head(reset) |
-                   pio::check_errors_rowgemm(reset));
+                   pio::check_errors_rowgemm(reset) | pio::check_errors_pixel_head(reset));
 }
 bool checked_build() { return PIO_CHECKS != 0; }
 // checked builds, outside graph capture: wait for the kernel just launched and raise on any
@@ -1590,6 +1595,85 @@ void pixel_ce_bwd(Tensor h, Tensor w, Tensor b, Tensor labels, Tensor wts, Tenso
                            db.data_ptr<float>(), stream());
 }
 
+// Inference head (pixel_head.hip pixel_predict_kernel): h (R = B·Q, C), one row per query pixel →
+// [classes (R) uint8, conf (R) fp32, class_map (B, npix) uint8, confusion partials
+// (blocks, K·K) int32 — only with labels].  class_map is cleared on the stream before the launch;
+// rows with qvalid False and indices outside [0, npix) leave it untouched.
+std::vector<Tensor> pixel_predict(Tensor h, Tensor w, Tensor b, Tensor qidx, Tensor qvalid, int64_t Q, int64_t npix,
+                                  OptT labels) {
+  CHECK_DT(h, torch::kFloat32); CHECK_DT(w, torch::kFloat32); CHECK_DT(b, torch::kFloat32);
+  CHECK_DT(qidx, torch::kInt64); CHECK_DT(qvalid, torch::kBool);
+  TORCH_CHECK(h.dim() == 2 && h.is_contiguous() && w.dim() == 2 && w.is_contiguous() && b.is_contiguous() &&
+                  qidx.is_contiguous() && qvalid.is_contiguous(), "pixel_predict: contiguous h (R, C), w (K, C)");
+  const int C = (int)h.size(1), K = (int)w.size(0);
+  const long long R = h.size(0);
+  TORCH_CHECK((C == 32 || C == 64 || C == 128) && K >= 2 && K <= 4 && w.size(1) == C && b.numel() == K,
+              "pixel_predict: C in {32, 64, 128}, 2 <= K <= 4");
+  TORCH_CHECK(Q > 0 && npix > 0 && R % Q == 0 && qidx.numel() == R && qvalid.numel() == R,
+              "pixel_predict: R = B * Q rows, one qidx / qvalid entry per row");
+  CHECK_CUDA(h);
+  TORCH_CHECK(w.get_device() == h.get_device() && b.get_device() == h.get_device() &&
+                  qidx.get_device() == h.get_device() && qvalid.get_device() == h.get_device(),
+              "pixel_predict: every operand on h's device");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(h.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
+              "pixel_predict: 16-byte aligned rows");
+  const int64_t* lab = nullptr;
+  if (labels.has_value()) {
+    CHECK_DT(*labels, torch::kInt64);
+    TORCH_CHECK(labels->is_contiguous() && labels->numel() == R && labels->get_device() == h.get_device(),
+                "pixel_predict: one contiguous label per row, on h's device");
+    lab = labels->data_ptr<int64_t>();
+  }
+  auto u8 = h.options().dtype(torch::kUInt8);
+  Tensor classes = torch::empty({R}, u8), conf = torch::empty({R}, h.options());
+  Tensor cmap = torch::empty({R / Q, npix}, u8);
+  if (cmap.numel() > 0) {
+    const hipError_t e = hipMemsetAsync(cmap.data_ptr(), 0, (size_t)cmap.numel(), stream());
+    TORCH_CHECK(e == hipSuccess, "pixel_predict: clearing the class map failed: ", hipGetErrorString(e));
+  }
+  std::vector<Tensor> out{classes, conf, cmap};
+  Tensor cpart;
+  if (lab != nullptr) {  // every block of the launch stores its whole partial row
+    auto i32 = h.options().dtype(torch::kInt32);
+    cpart = R > 0 ? torch::empty({pio::pixel_ce_blocks(R), K * K}, i32) : torch::zeros({1, K * K}, i32);
+    out.push_back(cpart);
+  }
+  pio::pixel_predict_launch(C, K, f32p(h), f32p(w), f32p(b), qidx.data_ptr<int64_t>(), qvalid.data_ptr<bool>(), lab, R,
+                            Q, npix, classes.data_ptr<uint8_t>(), conf.data_ptr<float>(), cmap.data_ptr<uint8_t>(),
+                            lab != nullptr ? cpart.data_ptr<int>() : nullptr, stream());
+  checked_sync("pixel_predict");
+  return out;
+}
+
+// img (B, npix) fp32 → [values (B, cap, 1) fp32, index (B, cap) int64, kmask (B, cap) bool,
+// count (B) int32]: the pixels with img != 0 in flat order (pixel_head.hip nonzero_compact);
+// cap = 0 only counts.  segs / tile: segments per sample (1..256) and loads per thread and tile
+// (4 or 8); 0 picks the measured default (profiles/lartpc_segment.md).
+constexpr int kNonzeroSegs = 64, kNonzeroTile = 4;
+std::vector<Tensor> nonzero_compact(Tensor img, int64_t cap, int64_t segs, int64_t tile) {
+  CHECK_CUDA(img);
+  CHECK_DT(img, torch::kFloat32);
+  TORCH_CHECK(img.dim() == 2 && img.is_contiguous(), "nonzero_compact: img must be (B, npix) contiguous");
+  const int64_t B = img.size(0), npix = img.size(1);
+  TORCH_CHECK(B > 0 && B <= 65535 && npix > 0 && npix < (1ll << 31) && cap >= 0, "nonzero_compact: bad shape or capacity");
+  TORCH_CHECK(segs >= 0 && segs <= 256 && (tile == 0 || tile == 4 || tile == 8), "nonzero_compact: segs in [0, 256], tile in {0, 4, 8}");
+  const int V = tile == 0 ? kNonzeroTile : (int)tile;
+  int S = (int)segs;
+  if (S == 0) {  // at most kNonzeroSegs segments, none shorter than one tile
+    const int64_t tiles = (npix + 256 * V - 1) / (256 * V);
+    S = (int)std::min<int64_t>(kNonzeroSegs, tiles);
+  }
+  Tensor values = torch::empty({B, cap, 1}, img.options()), index = torch::empty({B, cap}, img.options().dtype(torch::kInt64));
+  Tensor kmask = torch::empty({B, cap}, img.options().dtype(torch::kBool));
+  Tensor count = torch::empty({B}, img.options().dtype(torch::kInt32));
+  Tensor segcount;
+  if (S > 1) segcount = torch::empty({B, S}, count.options());
+  pio::nonzero_compact_launch(f32p(img), (int)B, npix, cap, S, V, S > 1 ? segcount.data_ptr<int>() : nullptr,
+                              values.data_ptr<float>(), index.data_ptr<int64_t>(), kmask.data_ptr<bool>(),
+                              count.data_ptr<int>(), stream());
+  return {values, index, kmask, count};
+}
+
 void adamw(Tensor p, Tensor g, Tensor m, Tensor v, OptT shadow, Tensor hyper, double eps, double wd, double clip,
            double gscale, bool l2, bool zero_grad, OptT loss_src, OptT loss_ring, OptT norm_part) {
   TORCH_CHECK(clip <= 0 || (norm_part.has_value() && norm_part->is_contiguous() && norm_part->numel() >= kSumsqParts &&
@@ -2016,6 +2100,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("batch_sum2", &batch_sum2, py::arg("a"), py::arg("b"), py::arg("ob_acc") = py::none());
   m.def("pixel_ce_fwd", &pixel_ce_fwd);
   m.def("pixel_ce_bwd", &pixel_ce_bwd);
+  m.def("pixel_predict", &pixel_predict, py::arg("h"), py::arg("w"), py::arg("b"), py::arg("qidx"), py::arg("qvalid"),
+        py::arg("Q"), py::arg("npix"), py::arg("labels") = py::none());
+  m.def("nonzero_compact", &nonzero_compact, py::arg("img"), py::arg("cap"), py::arg("segs") = 0, py::arg("tile") = 0);
   m.def("stage_step", &stage_step, py::arg("dsts"), py::arg("srcs"), py::arg("hyper_dst") = py::none(),
         py::arg("hyper") = std::vector<double>{}, py::arg("seed_dst") = py::none(),
         py::arg("seeds") = std::vector<int64_t>{});

@@ -11,6 +11,10 @@
 //        dH = coefᵀ·W (written once), dW = Σ coef ⊗ h, db = Σ coef (per-block partials)
 // Two one-block finalize kernels sum the partials in a fixed order (deterministic; no
 // atomics): the loss / accuracies, and dW / db added into the parameter gradients.
+//
+// Inference (further down): pixel_predict — the same row pass writing class, confidence, the
+// per-sample class map and an optional confusion count, and nonzero_compact — the device-side
+// sparsifier that turns a dense image into the encoder's (values, index, kmask) operands.
 #include "common.h"
 
 namespace pio {
@@ -285,6 +289,219 @@ void pixel_ce_bwd_launch(int C, int K, const float* H, const float* W, const flo
   hipLaunchKernelGGL(pixel_ce_wgrad_kernel, dim3((NP + 63) / 64), dim3(1024), 0, st, part, pixel_ce_blocks(R), NP,
                      K * C, dW, db);
 }
+
+// ---- inference: class / confidence per row, the class map and a confusion count --------------
+// The forward kernel's row layout and logits; nothing is reduced but the optional K×K confusion
+// count (rows = label, columns = prediction), kept per thread in registers and stored as one int32
+// partial row per block (no atomics; the caller sums the rows).  Lane sub == 0 of a row stores
+// classes[r] / conf[r] (0 / 0 on an invalid row) and, on a valid row, the byte
+// cmap[(r / Q)·npix + qidx[r]]: every build skips an index outside [0, npix), the checked build
+// also flags it.  Valid indices of one sample must be distinct (two rows at one pixel race).
+template <int C, int K>
+__global__ __launch_bounds__(256) void pixel_predict_kernel(const float* __restrict__ H, const float* __restrict__ W,
+                                                            const float* __restrict__ bias,
+                                                            const int64_t* __restrict__ qidx,
+                                                            const bool* __restrict__ qvalid,
+                                                            const int64_t* __restrict__ labels, long long R,
+                                                            long long Q, long long npix,
+                                                            uint8_t* __restrict__ classes, float* __restrict__ conf,
+                                                            uint8_t* __restrict__ cmap, int* __restrict__ cpart) {
+  constexpr int CPL = C / 16, KK = K * K;
+  const int l = lane_id(), w = wave_id(), sub = l & 15, grp = l >> 4;
+  float wk[K][CPL], bk[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    load_row<CPL>(W + k * C + sub * CPL, wk[k]);
+    bk[k] = bias[k];
+  }
+  int cnt[KK];
+#pragma unroll
+  for (int s = 0; s < KK; ++s) cnt[s] = 0;
+  for (long long r = (long long)blockIdx.x * PH_ROWS + w * 4 + grp; r < R; r += (long long)gridDim.x * PH_ROWS) {
+    float h[CPL], z[K];
+    load_row<CPL>(H + r * C + sub * CPL, h);
+    const bool valid = qvalid[r];
+    const long long pix = qidx[r];
+    const long long lab64 = labels != nullptr ? labels[r] : -1;
+    row_logits<C, K>(h, wk, bk, z);
+    float m = z[0];
+    int pred = 0;
+#pragma unroll
+    for (int k = 1; k < K; ++k) {
+      pred = z[k] > m ? k : pred;
+      m = fmaxf(m, z[k]);
+    }
+    float se = 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) se += __expf(z[k] - m);
+    if (sub == 0) {
+      classes[r] = valid ? (uint8_t)pred : (uint8_t)0;
+      conf[r] = valid ? 1.f / se : 0.f;
+      if (valid) {
+        const bool inside = pix >= 0 && pix < npix;
+        if (inside) cmap[(r / Q) * npix + pix] = (uint8_t)pred;
+        else pio_flag(kErrGatherRow);
+        if (lab64 >= 0 && lab64 < K) {
+          const int cell = (int)lab64 * K + pred;
+#pragma unroll
+          for (int s = 0; s < KK; ++s) cnt[s] += s == cell ? 1 : 0;
+        }
+      }
+    }
+  }
+  if (cpart == nullptr) return;
+  // only lanes 0, 16, 32, 48 of a wave counted
+  __shared__ int sred[4][KK];
+#pragma unroll
+  for (int s = 0; s < KK; ++s) {
+    int v = cnt[s];
+    v += __shfl_xor(v, 16, 64);
+    v += __shfl_xor(v, 32, 64);
+    if (l == 0) sred[w][s] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < KK)
+    cpart[(long long)blockIdx.x * KK + threadIdx.x] =
+        sred[0][threadIdx.x] + sred[1][threadIdx.x] + sred[2][threadIdx.x] + sred[3][threadIdx.x];
+}
+
+// cpart: (pixel_ce_blocks(R), K·K) int32 when labels are given, else nullptr; cmap (R / Q, npix) is
+// zero-filled by the caller before this launch
+void pixel_predict_launch(int C, int K, const float* H, const float* W, const float* bias, const int64_t* qidx,
+                          const bool* qvalid, const int64_t* labels, long long R, long long Q, long long npix,
+                          uint8_t* classes, float* conf, uint8_t* cmap, int* cpart, hipStream_t st) {
+  if (R > 0) PH_DISPATCH(pixel_predict_kernel, H, W, bias, qidx, qvalid, labels, R, Q, npix, classes, conf, cmap, cpart);
+}
 #undef PH_DISPATCH
+
+// ---- nonzero_compact: dense image (B, npix) → the sparse operands of the encoder ----------------
+// Ordered stream compaction of the pixels with img != 0 (-0.0 is zero, NaN is not), per sample:
+// slot j < min(count, cap) of values / index / kmask holds the j-th such pixel in flat order
+// (kmask False), every later slot (0, 0, True): what data/lartpc.py sparse_collate builds on the
+// CPU.  count is the true number of non-zero pixels, also beyond cap.
+//
+// A sample is cut into S segments of whole tiles.  With S > 1 a first launch counts each
+// segment; the scatter launch (S × B blocks) turns the segment counts into its base slot and the
+// sample total, then walks its segment in tiles of 256·V pixels: V coalesced loads per thread
+// (element j·256 + t of the tile; no alignment assumed), one ballot per load, wave totals through
+// a ping-pong LDS buffer (one barrier per tile), the running base in a register of every thread.
+// The order comes from the scan alone (no atomics).  With S = 1 the count launch is skipped; a
+// counting call (cap = 0) with S > 1 skips the walk instead (its total is the sum of the counts).
+constexpr int NZ_THREADS = 256, NZ_WAVES = NZ_THREADS / 64;
+
+__device__ __forceinline__ int wave_isum(int v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(NZ_THREADS) void nonzero_count_kernel(const float* __restrict__ img, long long npix,
+                                                                   long long seg, int* __restrict__ segcount) {
+  const int s = blockIdx.x, b = blockIdx.y, S = gridDim.x;
+  const long long start = (long long)s * seg, end = start + seg < npix ? start + seg : npix;
+  const float* p = img + (long long)b * npix;
+  int n = 0;
+  for (long long i = start + threadIdx.x; i < end; i += NZ_THREADS) n += p[i] != 0.f ? 1 : 0;
+  n = wave_isum(n);
+  __shared__ int sW[NZ_WAVES];
+  if (lane_id() == 0) sW[wave_id()] = n;
+  __syncthreads();
+  if (threadIdx.x == 0) segcount[(long long)b * S + s] = sW[0] + sW[1] + sW[2] + sW[3];
+}
+
+template <int V>
+__global__ __launch_bounds__(NZ_THREADS) void nonzero_scatter_kernel(const float* __restrict__ img, long long npix,
+                                                                     long long seg, long long cap,
+                                                                     const int* __restrict__ segcount,
+                                                                     float* __restrict__ values,
+                                                                     int64_t* __restrict__ index,
+                                                                     bool* __restrict__ kmask, int* __restrict__ count) {
+  constexpr int TILE = NZ_THREADS * V;
+  const int s = blockIdx.x, b = blockIdx.y, S = gridDim.x;
+  const int l = lane_id(), w = wave_id();
+  __shared__ int sW[2][V][NZ_WAVES];
+  __shared__ int sR[2][NZ_WAVES];
+  long long run = 0, total = 0;  // slots of the sample before this block's next tile; the sample's count
+  if (S > 1) {                   // S <= NZ_THREADS: one segment count per thread
+    const int c = (int)threadIdx.x < S ? segcount[(long long)b * S + threadIdx.x] : 0;
+    const int before = wave_isum((int)threadIdx.x < s ? c : 0), all = wave_isum(c);
+    if (l == 0) { sR[0][w] = before; sR[1][w] = all; }
+    __syncthreads();
+    run = sR[0][0] + sR[0][1] + sR[0][2] + sR[0][3];
+    total = sR[1][0] + sR[1][1] + sR[1][2] + sR[1][3];
+  }
+  const long long start = (long long)s * seg, end = start + seg < npix ? start + seg : npix;
+  const float* p = img + (long long)b * npix;
+  float* vo = values + (long long)b * cap;
+  int64_t* io = index + (long long)b * cap;
+  bool* mo = kmask + (long long)b * cap;
+  const uint64_t below = (1ull << l) - 1ull;
+  int buf = 0;
+  // a counting call (cap == 0) with S > 1 already has its total: no second read of the image
+  const bool walk = S == 1 || cap > 0;
+  for (long long t0 = start; walk && t0 < end; t0 += TILE, buf ^= 1) {
+    float v[V];
+    int pre[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      const long long i = t0 + j * NZ_THREADS + threadIdx.x;
+      v[j] = i < end ? p[i] : 0.f;
+    }
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      const uint64_t m = __ballot(v[j] != 0.f);
+      pre[j] = __popcll(m & below);
+      if (l == 0) sW[buf][j][w] = __popcll(m);
+    }
+    lds_sync();
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      int woff = 0, tot = 0;
+#pragma unroll
+      for (int k = 0; k < NZ_WAVES; ++k) {
+        const int c = sW[buf][j][k];
+        woff += k < w ? c : 0;
+        tot += c;
+      }
+      const long long pos = run + woff + pre[j];
+      if (v[j] != 0.f && pos < cap) {
+        vo[pos] = v[j];
+        io[pos] = t0 + j * NZ_THREADS + threadIdx.x;
+        mo[pos] = false;
+      }
+      run += tot;
+    }
+  }
+  if (S == 1) total = run;
+  // padding slots [min(total, cap), cap) of the sample, dealt over its S blocks
+  for (long long j = (total < cap ? total : cap) + (long long)s * NZ_THREADS + threadIdx.x; j < cap;
+       j += (long long)S * NZ_THREADS) {
+    vo[j] = 0.f;
+    io[j] = 0;
+    mo[j] = true;
+  }
+  if (s == 0 && threadIdx.x == 0) count[b] = (int)total;
+}
+
+// pixels per segment for S segments: whole tiles of 256·V
+long long nonzero_seg_len(long long npix, int S, int V) {
+  const long long tile = (long long)NZ_THREADS * V, per = (npix + S - 1) / S;
+  return (per + tile - 1) / tile * tile;
+}
+
+// S in [1, 256] segments per sample, V in {4, 8} loads per thread and tile; segcount: (B, S) int32
+// scratch (unused when S == 1)
+void nonzero_compact_launch(const float* img, int B, long long npix, long long cap, int S, int V, int* segcount,
+                            float* values, int64_t* index, bool* kmask, int* count, hipStream_t st) {
+  const long long seg = nonzero_seg_len(npix, S, V);
+  const dim3 g(S, B), t(NZ_THREADS);
+  if (S > 1) hipLaunchKernelGGL(nonzero_count_kernel, g, t, 0, st, img, npix, seg, segcount);
+  if (V == 8)
+    hipLaunchKernelGGL(nonzero_scatter_kernel<8>, g, t, 0, st, img, npix, seg, cap, segcount, values, index, kmask, count);
+  else
+    hipLaunchKernelGGL(nonzero_scatter_kernel<4>, g, t, 0, st, img, npix, seg, cap, segcount, values, index, kmask, count);
+}
+
+unsigned check_errors_pixel_head(bool reset) { return pio_read_errors(reset); }
 
 }  // namespace pio

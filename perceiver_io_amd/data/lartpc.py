@@ -11,6 +11,10 @@ DataLoader workers:
 
 K and Q are the batch maxima rounded up to a multiple of ``bucket``.  That gives a handful of
 distinct shapes, so the step engine keeps one captured hipGraph per shape.
+
+For inference the key tensors are built on the device instead: the ``nonzero_compact`` kernel
+(``LArPerceiver.segment``) returns, at the same capacity, bitwise the ``values / index / kmask``
+of ``sparse_collate`` from a dense image batch that is already on the GPU.
 """
 from __future__ import annotations
 

@@ -20,11 +20,16 @@ discarded.
 
 Parameter gradients (including the zero rows of the 262,144 × C output-query table) equal the
 dense computation's.  ``tests/test_lartpc.py`` checks this against the dense eager model.
-``forward`` keeps the dense per-pixel logits for inference.
+``forward`` keeps the dense per-pixel logits of the reference.
+
+Inference runs sparse too: ``LArPerceiver.segment`` compacts a dense event to its non-zero pixels
+on the device, encodes those, decodes the same pixels and writes their classes into a uint8
+class map (``segment_sparse`` takes already sparse operands).  The class of a lit pixel equals the
+dense model's ``argmax``; unlit pixels read as background, which is what the reference displays.
 """
 from __future__ import annotations
 
-from typing import Dict, Sequence, Tuple
+from typing import Dict, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -35,6 +40,16 @@ from .uresnet import UResNet
 
 NUM_CLASSES = 3
 CLASS_WEIGHTS = (0.0, 1.0, 1.0)  # background, track, shower (reference run.py:238-240)
+
+
+class Segmentation(NamedTuple):
+    """Result of :meth:`LArPerceiver.segment` / :meth:`LArPerceiver.segment_sparse`."""
+
+    classes: torch.Tensor              # (B, Q) uint8: class of each query pixel, 0 on padding slots
+    confidence: torch.Tensor           # (B, Q) fp32: softmax probability of that class, 0 on padding
+    class_map: torch.Tensor            # (B, H·W) uint8: the classes at their pixels, 0 elsewhere
+    confusion: Optional[torch.Tensor]  # (3, 3) int64, rows = label, columns = prediction (with labels)
+    count: torch.Tensor                # (B,) int32: non-zero pixels per sample (may exceed the capacity)
 
 
 def sparse_inputs(adapter: ImageInputAdapter, values: torch.Tensor, index: torch.Tensor) -> torch.Tensor:
@@ -110,6 +125,65 @@ class LArPerceiver(torch.nn.Module):
         values, index, kmask, qidx, qlab = batch
         h = self.sparse_hidden(values, index, kmask, qidx)
         return pixel_ce(h, self.perceiver.decoder.output_adapter.linear, qlab, weights)
+
+
+    def segment_sparse(self, values, index, kmask, qidx=None, qmask=None, labels=None) -> Segmentation:
+        """Class map of a sparse batch (``sparse_collate`` layout, or :func:`nonzero_compact`'s).
+
+        With ``qidx=None`` the queries are the keys: every lit pixel is classified (``qidx =
+        index``, valid where ``~kmask``).  Otherwise ``qidx`` (B, Q) names the pixels to classify and
+        ``qmask`` (B, Q) bool is True on its padding slots (None: all valid).  ``labels`` (B, Q)
+        int64 at the query pixels add the confusion matrix.  The valid query pixels of one sample
+        must be distinct (see ``ops.pixel_head.pixel_predict``).  Runs under ``no_grad``: the
+        sparse encoder and decoder, then one fused head pass; dense logits never exist."""
+        from ..ops.pixel_head import pixel_predict
+
+        with torch.no_grad():
+            if qidx is None:
+                qidx, qvalid = index, ~kmask
+            else:
+                qvalid = ~qmask if qmask is not None else torch.ones_like(qidx, dtype=torch.bool)
+            h = self.sparse_hidden(values, index, kmask, qidx)
+            classes, conf, cmap, confusion = pixel_predict(h, self.perceiver.decoder.output_adapter.linear, qidx, qvalid,
+                                                           self.size * self.size, labels)
+            return Segmentation(classes, conf, cmap, confusion, (~kmask).sum(1).to(torch.int32))
+
+    def segment(self, img, capacity: Optional[int] = None, bucket: int = 2048, labels=None) -> Segmentation:
+        """Class map ``(B, H·W)`` uint8 of dense events ``img`` (B, H, W) or (B, H·W): the class of
+        every non-zero pixel, 0 elsewhere (what the reference displays, ``argmax · (x != 0)``).
+
+        The image is compacted to its non-zero pixels (on the GPU by ``nonzero_compact``, in flat
+        order, exactly the operands ``sparse_collate`` builds) and goes through
+        :meth:`segment_sparse`.  ``capacity=None`` sizes the key set from the data: one counting
+        pass, then ``count.max()`` is read on the host — the only synchronisation — and rounded up
+        to ``bucket`` so that shapes repeat.  With ``capacity`` given nothing waits on the device;
+        pixels past the capacity are not classified, and ``Segmentation.count`` (the true number of
+        non-zero pixels per sample) lets the caller detect that.  Dense ``labels`` (B, H·W) are
+        gathered at the classified pixels for the confusion matrix."""
+        from .. import ops
+        from ..data.lartpc import _round_up
+
+        b = img.shape[0]
+        flat = img.reshape(b, -1).float().contiguous()
+        kern = ops.fused.kernels(flat) if ops.use_hip(flat) else ops.emulation
+        if capacity is None:
+            count = kern.nonzero_compact(flat, 0)[3]
+            capacity = _round_up(int(count.max()), bucket)
+        values, index, kmask, count = kern.nonzero_compact(flat, int(capacity))
+        qlab = labels.reshape(b, -1).long().gather(1, index) if labels is not None else None
+        seg = self.segment_sparse(values, index, kmask, labels=qlab)
+        return seg._replace(count=count)
+
+
+def iou(confusion: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(per-class IoU (K,), mean IoU)`` of a confusion matrix (rows = label, columns =
+    prediction): ``TP / (label + predicted − TP)``; NaN for a class that occurs in neither, and
+    the mean runs over the classes present."""
+    c = confusion.double()
+    tp = c.diagonal()
+    union = c.sum(0) + c.sum(1) - tp
+    per = torch.where(union > 0, tp / union.clamp(min=1), torch.full_like(tp, float("nan")))
+    return per, per[union > 0].mean() if bool((union > 0).any()) else per.new_tensor(float("nan"))
 
 
 def accuracies(pred: torch.Tensor, lab: torch.Tensor) -> Dict[str, torch.Tensor]:

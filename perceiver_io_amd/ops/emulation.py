@@ -770,6 +770,54 @@ def pixel_ce_bwd(h, w, b, labels, wts, gout, stats, dH, dW, db):
     db += coef.sum(0)
 
 
+def pixel_predict(h, w, b, qidx, qvalid, Q, npix, labels=None):
+    """[classes (R) uint8, conf (R) fp32, class_map (R / Q, npix) uint8 (+ confusion partials
+    (1, K·K) int32 with labels)] of pixel_head.hip ``pixel_predict_kernel``: argmax with the lowest
+    class winning a tie, the softmax probability of that class, 0 / 0 on invalid rows; valid rows
+    with qidx inside [0, npix) write their class into the zero-filled map."""
+    K = w.shape[0]
+    z = _pixel_logits(h, w, b)
+    R = z.shape[0]
+    valid = qvalid.reshape(-1)
+    zmax = z.max(-1, keepdim=True).values
+    ks = torch.arange(K, device=z.device).expand_as(z)
+    pred = torch.where(z == zmax, ks, torch.full_like(ks, K)).min(-1).values.clamp(max=K - 1)
+    p = 1.0 / torch.exp(z - zmax).sum(-1)
+    classes = torch.where(valid, pred, torch.zeros_like(pred)).to(torch.uint8)
+    conf = torch.where(valid, p, torch.zeros_like(p))
+    pix = qidx.reshape(-1)
+    put = valid & (pix >= 0) & (pix < npix)
+    cmap = torch.zeros(R // Q, npix, dtype=torch.uint8, device=h.device)
+    flat = (torch.arange(R, device=h.device) // Q) * npix + pix
+    cmap.view(-1)[flat[put]] = classes[put]
+    out = [classes, conf, cmap]
+    if labels is not None:
+        lab = labels.reshape(-1)
+        ok = valid & (lab >= 0) & (lab < K)
+        out.append(torch.bincount(lab[ok] * K + pred[ok], minlength=K * K).to(torch.int32).view(1, K * K))
+    return out
+
+
+def nonzero_compact(img, cap, segs=0, tile=0):
+    """[values (B, cap, 1), index (B, cap) int64, kmask (B, cap) bool, count (B) int32] of
+    pixel_head.hip ``nonzero_compact``: the pixels with ``img != 0`` in flat order, padding slots
+    (0, 0, True); ``count`` is the true number of non-zero pixels, also beyond ``cap``."""
+    B, npix = img.shape
+    nz = img != 0
+    count = nz.sum(1)
+    pos = torch.cumsum(nz, 1) - 1
+    keep = nz & (pos < cap)
+    values = torch.zeros(B, cap, dtype=img.dtype, device=img.device)
+    index = torch.zeros(B, cap, dtype=torch.long, device=img.device)
+    kmask = torch.ones(B, cap, dtype=torch.bool, device=img.device)
+    bi, pi = torch.nonzero(keep, as_tuple=True)
+    slot = pos[bi, pi]
+    values[bi, slot] = img[bi, pi]
+    index[bi, slot] = pi
+    kmask[bi, slot] = False
+    return [values.unsqueeze(-1), index, kmask, count.to(torch.int32)]
+
+
 # ---- per-sample latent-block kernels (csrc/sample_block.hip): 32 latents, 4 heads -------------
 # the same operands, bf16 rounding points and outputs as sb_fwd / sb_bwd / sb_wgrad
 _SB_N, _SB_H = 32, 4

@@ -7,10 +7,13 @@ per-class accuracies of the LArTPC experiment (reference ``run.py:190-206``).  L
 reach memory: the forward pass reads each row of ``h`` once and writes per-block partial sums.
 The backward pass reads it again and writes ``dH`` plus per-block ``dW | db`` partials, which are
 summed in a fixed order (deterministic).
+
+``pixel_predict`` is the inference counterpart: class, confidence, the per-sample class map and
+an optional confusion matrix from the same single pass over ``h``.
 """
 from __future__ import annotations
 
-from typing import Dict, Tuple
+from typing import Dict, Optional, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -85,3 +88,40 @@ def pixel_ce(h: torch.Tensor, linear: torch.nn.Linear, labels: torch.Tensor,
         hit = ((pred == lab) & sel).sum()
         out[name] = torch.where(n > 0, hit.float() / n.clamp(min=1).float(), torch.zeros((), device=lab.device))
     return loss, out
+
+
+def pixel_predict(h: torch.Tensor, linear: torch.nn.Linear, qidx: torch.Tensor, qvalid: torch.Tensor, npix: int,
+                  labels: Optional[torch.Tensor] = None):
+    """Per-pixel prediction of ``linear(h)`` without logits in memory (``pixel_predict_kernel``).
+
+    ``h`` (B, Q, C): decoder output at the query pixels ``qidx`` (B, Q) int64 (flat pixel index);
+    ``qvalid`` (B, Q) bool marks the real queries.  Returns
+
+    * ``classes`` (B, Q) uint8 — argmax class, the lowest class on an exact tie; 0 on invalid rows;
+    * ``conf`` (B, Q) fp32 — the softmax probability of that class; 0 on invalid rows;
+    * ``class_map`` (B, npix) uint8 — zero (background) except ``class_map[b, qidx[b, q]] =
+      classes[b, q]`` for the valid rows.  An index outside [0, npix) is skipped (the row keeps its
+      ``classes`` / ``conf`` entry; the checked build raises).  The valid indices of one sample must
+      be distinct, as ``sparse_collate`` and ``nonzero_compact`` build them: with duplicates, which
+      row's class lands in the map is unspecified;
+    * ``confusion`` (K, K) int64, rows = label, columns = prediction, over the valid rows with
+      ``0 <= label < K`` — ``None`` without ``labels`` (B, Q) int64.
+
+    No gradient flows through any output."""
+    K = linear.weight.shape[0]
+    B, Q, C = h.shape
+    with torch.no_grad():
+        h2 = h.reshape(B * Q, C).float().contiguous()
+        idx = qidx.reshape(-1).long().contiguous()
+        val = qvalid.reshape(-1).bool().contiguous()
+        lab = labels.reshape(-1).long().contiguous() if labels is not None else None
+        if _supported(h, linear.weight):
+            from .fused import kernels
+
+            kern = kernels(h)
+        else:
+            from . import emulation as kern
+        out = kern.pixel_predict(h2, linear.weight.detach().float().contiguous(), linear.bias.detach().float().contiguous(),
+                                 idx, val, Q, int(npix), lab)
+        conf = out[3].sum(0, dtype=torch.int64).view(K, K) if lab is not None else None
+        return out[0].view(B, Q), out[1].view(B, Q), out[2], conf

@@ -31,6 +31,12 @@ tfevents/JSONL.  With the fused optimizer, ``optimizer_state_dict`` covers the t
 parameters.  The unused U-ResNet never has a gradient, and torch's Adam skips it too.
 
     python run.py [--epochs 10] [--events 64] [--size 512] [--batch-size 4] [--dense] [--engine eager]
+
+``--segment CKPT --out DIR`` trains nothing: it loads ``model_state_dict`` from the checkpoint,
+segments the validation events through ``LArPerceiver.segment`` (sparse, no dense logits) and
+writes one uint8 H×W class map ``event_<i>.npy`` per event, then prints the per-class IoU.
+
+    python run.py --segment ckpt/model_9.ckpt --out segmented [--val-events 8] [--size 512]
 """
 from __future__ import annotations
 
@@ -46,7 +52,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from perceiver_io_amd.data.lartpc import SparseCollator  # noqa: E402
 from perceiver_io_amd.data.synthetic import SyntheticLArTPC  # noqa: E402
-from perceiver_io_amd.models.lartpc import LArPerceiver, accuracies, class_weights  # noqa: E402
+from perceiver_io_amd.models.lartpc import LArPerceiver, accuracies, class_weights, iou  # noqa: E402
 from perceiver_io_amd.train.loggers import TensorBoardLogger  # noqa: E402
 
 __all__ = ["LArPerceiver", "accuracies", "main"]
@@ -73,6 +79,29 @@ def make_step_fn(model, weights, sparse: bool, metrics: dict):
     return loss_fn
 
 
+def segment_events(model, a, dev):
+    """``--segment``: ``event_<i>.npy`` (uint8 H×W class map: the class of every non-zero pixel, 0
+    elsewhere) for each validation event, and the per-class IoU against the synthetic labels."""
+    import numpy as np
+
+    state = torch.load(a.segment, map_location=dev, weights_only=True)
+    model.load_state_dict(state["model_state_dict"])
+    model.eval()
+    os.makedirs(a.out, exist_ok=True)
+    val = torch.utils.data.DataLoader(SyntheticLArTPC(a.val_events, a.size, seed=1), batch_size=a.batch_size)
+    confusion, n = None, 0
+    for img, lab in val:
+        seg = model.segment(img.to(dev), bucket=a.bucket, labels=lab.to(dev))
+        confusion = seg.confusion if confusion is None else confusion + seg.confusion
+        for m in seg.class_map.cpu().numpy():
+            np.save(os.path.join(a.out, f"event_{n}.npy"), m.reshape(a.size, a.size))
+            n += 1
+    per, mean = iou(confusion)
+    names = ("background", "track", "shower")
+    print(f"segmented {n} events -> {a.out}", flush=True)
+    print("IoU: " + ", ".join(f"{k} {float(v):.4f}" for k, v in zip(names, per)) + f", mean {float(mean):.4f}", flush=True)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--epochs", type=int, default=10)
@@ -91,10 +120,15 @@ def main(argv=None):
     ap.add_argument("--bucket", type=int, default=2048, help="sparse capacity rounding (keys / queries)")
     ap.add_argument("--log-every", type=int, default=1)
     ap.add_argument("--workers", type=int, default=1)
+    ap.add_argument("--segment", metavar="CKPT", default=None,
+                    help="no training: segment the validation events with this checkpoint and write class maps to --out")
+    ap.add_argument("--out", metavar="DIR", default="segmented", help="output directory of --segment")
     a = ap.parse_args(argv)
     dev = torch.device(a.device)
     torch.manual_seed(0)
     model = LArPerceiver(a.size).to(dev)
+    if a.segment is not None:
+        return segment_events(model, a, dev)
     weights = class_weights(dev)
     sparse = not a.dense
     collate = SparseCollator(a.bucket) if sparse else None
