@@ -10,6 +10,7 @@ Surface reproduced: subcommands ``fit|validate|test``; dotted flags ``--model.* 
 parse-time links (``trainer.default_root_dir→logger.save_dir``, ``experiment→logger.name``,
 ``trainer.max_steps→lr_scheduler.total_steps``, ``optimizer.lr→lr_scheduler.max_lr``) and
 instantiate-time links (``data.vocab_size/max_seq_len/num_classes/image_shape→model.*``);
+``--optimizer=<Class>`` (e.g. ``Lamb``) swaps the optimizer class, default AdamW;
 ``set_defaults``; optimizer / scheduler carried as ``{class_path, init_args}`` into the model;
 ``config.yaml`` saved into the log directory (overwrite).  Values are parsed with
 ``yaml.safe_load`` (lists, bools, numbers, null).
@@ -22,6 +23,7 @@ from __future__ import annotations
 import copy
 import inspect
 import os
+import re
 import sys
 from typing import Any, Dict, List, Optional
 
@@ -30,7 +32,13 @@ import yaml
 SUBCOMMANDS = ("fit", "validate", "test")
 
 
+# YAML 1.1 reads "1e-3" (no dot in the mantissa) as a string; on a command line it is a number
+_SCI_FLOAT = re.compile(r"[+-]?\d+[eE][+-]?\d+")
+
+
 def _parse_value(s: str):
+    if _SCI_FLOAT.fullmatch(s.strip()):
+        return float(s)
     try:
         return yaml.safe_load(s)
     except yaml.YAMLError:
@@ -71,6 +79,22 @@ def _signature_defaults(cls, skip=("self",)) -> Dict[str, Any]:
             continue
         out[name] = None if p.default is inspect.Parameter.empty else p.default
     return out
+
+
+def _optimizer_class(name: str):
+    """``--optimizer=<Class>``: a ``torch.optim`` class or this package's ``Lamb`` by name, or a
+    dotted class path."""
+    import torch
+
+    from ..ops import optim as own
+    from ..train.module import import_class
+
+    if "." in name:
+        return import_class(name)
+    cls = getattr(own, name, None) if name == "Lamb" else getattr(torch.optim, name, None)
+    if not (isinstance(cls, type) and issubclass(cls, torch.optim.Optimizer)):
+        raise SystemExit(f"unknown optimizer {name!r}; expected Lamb, a torch.optim class or a dotted class path")
+    return cls
 
 
 class CLIParser:
@@ -164,13 +188,6 @@ class CLI:
             sub, argv = argv[0], argv[1:]
         elif argv and not argv[0].startswith("-"):
             raise SystemExit(f"unknown subcommand {argv[0]!r}; expected one of {SUBCOMMANDS}")
-        cfg = self._base_config()
-        dfile = self.trainer_defaults_file if os.path.exists(self.trainer_defaults_file) else self.package_defaults_file
-        if os.path.exists(dfile):
-            with open(dfile) as f:
-                _merge(cfg, yaml.safe_load(f) or {})
-        for k, v in self.parser.defaults.items():
-            _set(cfg, k, copy.deepcopy(v))
         # pairs "--a.b=v" or "--a.b v"
         pairs = []
         i = 0
@@ -190,10 +207,33 @@ class CLI:
                 v = argv[i]
             pairs.append((k, v))
             i += 1
+        configs = []
         for k, v in pairs:
             if k == "config":
                 with open(v) as f:
-                    _merge(cfg, yaml.safe_load(f) or {})
+                    configs.append(yaml.safe_load(f) or {})
+        # --optimizer=<Class> (or a config file's optimizer.class) swaps the optimizer class before
+        # the defaults are laid down: --optimizer.* then default to that class's signature
+        okey = self.parser.optimizer[2] if self.parser.optimizer else None
+        oname = None
+        if okey is not None:
+            for c in configs:
+                if isinstance(c.get(okey), dict) and c[okey].get("class"):
+                    oname = c[okey]["class"]
+            for k, v in pairs:
+                if k == okey and isinstance(_parse_value(v), str):
+                    oname = _parse_value(v)
+            if oname is not None:
+                self.parser.optimizer = (_optimizer_class(oname),) + tuple(self.parser.optimizer[1:])
+        cfg = self._base_config()
+        dfile = self.trainer_defaults_file if os.path.exists(self.trainer_defaults_file) else self.package_defaults_file
+        if os.path.exists(dfile):
+            with open(dfile) as f:
+                _merge(cfg, yaml.safe_load(f) or {})
+        for k, v in self.parser.defaults.items():
+            _set(cfg, k, copy.deepcopy(v))
+        for c in configs:
+            _merge(cfg, c)
         for k, v in pairs:
             if k == "config":
                 continue
@@ -203,8 +243,12 @@ class CLI:
                 if not isinstance(cfg["data"], dict):
                     cfg["data"] = {}
                 cfg["data"]["class"] = val
+            elif k == okey and isinstance(val, str):
+                continue  # the class, taken above
             else:
                 _set(cfg, k, val)
+        if oname is not None:  # kept in config.yaml, so that --config <saved file> selects it again
+            cfg[okey]["class"] = oname
         for src, dst, fn, when in self.parser.links:
             if when == "parse":
                 val = _get(cfg, src)
@@ -264,7 +308,8 @@ class CLI:
         if self.parser.optimizer:
             ocls, link, key = self.parser.optimizer
             model_cfg[link.split(".", 1)[1]] = {"class_path": f"{ocls.__module__}.{ocls.__name__}".replace(
-                "torch.optim.adamw", "torch.optim"), "init_args": dict(cfg.get(key) or {})}
+                "torch.optim.adamw", "torch.optim"),
+                "init_args": {k: v for k, v in (cfg.get(key) or {}).items() if k != "class"}}
         if self.parser.lr_scheduler:
             scls, link, key = self.parser.lr_scheduler
             model_cfg[link.split(".", 1)[1]] = {"class_path": f"torch.optim.lr_scheduler.{scls.__name__}",

@@ -157,6 +157,10 @@ void nonzero_compact_launch(const float*, int, long long, long long, int, int, i
 unsigned check_errors_pixel_head(bool);
 void adamw_launch(float*, float*, float*, float*, uint16_t*, long long, const float*, float, float, float, float,
                   int, int, const float*, float*, int, const float*, hipStream_t);
+int lamb_chunk_elems();
+void lamb_launch(float*, float*, float*, float*, uint16_t*, long long, const float*, const long long*, long long,
+                 const int*, const float*, int, float*, float*, float, float, float, int, const float*, float*, int,
+                 const float*, hipStream_t);
 void cast_bf16_launch(const float*, uint16_t*, long long, hipStream_t);
 void reduce_probe_launch(const float*, float*, hipStream_t);
 void fold_replicas_launch(float*, float*, long long, int, hipStream_t);
@@ -1697,6 +1701,56 @@ void adamw(Tensor p, Tensor g, Tensor m, Tensor v, OptT shadow, Tensor hyper, do
                     clip > 0 ? f32p(*norm_part) : nullptr, stream());
 }
 
+// fused LAMB over the flat buffers (csrc/lamb.hip): chunk_tab (C, 3) int64 = (start, length, tensor),
+// tensor_tab (T, 2) int32 = (first chunk, chunks), tensor_opt (T, 2) fp32 = (weight decay, adapt);
+// partials: >= 2 C fp32 (per-chunk Σw², Σu²), trust: (T,) fp32 (written every step, kept)
+void lamb(Tensor p, Tensor g, Tensor m, Tensor v, OptT shadow, Tensor hyper, Tensor chunk_tab, Tensor tensor_tab,
+          Tensor tensor_opt, Tensor partials, Tensor trust, double eps, double clip, double gscale, bool zero_grad,
+          OptT loss_src, OptT loss_ring, OptT norm_part) {
+  TORCH_CHECK(clip <= 0 || (norm_part.has_value() && norm_part->is_contiguous() && norm_part->numel() >= kSumsqParts &&
+                            norm_part->scalar_type() == torch::kFloat32),
+              "lamb: clip > 0 needs norm_part (the sumsq partials of the gradient)");
+  CHECK_CUDA(p); CHECK_CUDA(g); CHECK_CUDA(m); CHECK_CUDA(v); CHECK_CUDA(hyper); CHECK_CUDA(chunk_tab);
+  CHECK_CUDA(tensor_tab); CHECK_CUDA(tensor_opt); CHECK_CUDA(partials); CHECK_CUDA(trust);
+  CHECK_DT(p, torch::kFloat32); CHECK_DT(g, torch::kFloat32); CHECK_DT(m, torch::kFloat32); CHECK_DT(v, torch::kFloat32);
+  TORCH_CHECK(p.is_contiguous() && g.is_contiguous() && m.is_contiguous() && v.is_contiguous());
+  TORCH_CHECK(p.numel() == g.numel() && p.numel() == m.numel() && p.numel() == v.numel());
+  uint16_t* sp = nullptr;
+  if (shadow.has_value()) {
+    CHECK_DT(*shadow, torch::kBFloat16);
+    TORCH_CHECK(shadow->is_contiguous() && shadow->numel() == p.numel());
+    sp = reinterpret_cast<uint16_t*>(shadow->data_ptr());
+  }
+  TORCH_CHECK(((reinterpret_cast<uintptr_t>(p.data_ptr()) | reinterpret_cast<uintptr_t>(g.data_ptr()) |
+                reinterpret_cast<uintptr_t>(m.data_ptr()) | reinterpret_cast<uintptr_t>(v.data_ptr())) & 15) == 0 &&
+                  (reinterpret_cast<uintptr_t>(sp) & 7) == 0,
+              "lamb: the flat buffers must be 16-byte aligned (the shadow 8-byte)");
+  CHECK_DT(chunk_tab, torch::kInt64); CHECK_DT(tensor_tab, torch::kInt32); CHECK_DT(tensor_opt, torch::kFloat32);
+  CHECK_DT(partials, torch::kFloat32); CHECK_DT(trust, torch::kFloat32);
+  const int64_t C = chunk_tab.size(0), T = tensor_tab.size(0);
+  TORCH_CHECK(chunk_tab.dim() == 2 && chunk_tab.size(1) == 3 && chunk_tab.is_contiguous() && tensor_tab.dim() == 2 &&
+                  tensor_tab.size(1) == 2 && tensor_tab.is_contiguous() && tensor_opt.is_contiguous() &&
+                  tensor_opt.dim() == 2 && tensor_opt.size(0) == T && tensor_opt.size(1) == 2,
+              "lamb: chunk_tab (C, 3) int64, tensor_tab (T, 2) int32, tensor_opt (T, 2) fp32, contiguous");
+  TORCH_CHECK(partials.is_contiguous() && partials.numel() >= 2 * C && trust.is_contiguous() && trust.numel() >= T &&
+                  hyper.numel() >= 8 && C < (int64_t(1) << 31) && T < (int64_t(1) << 31),
+              "lamb: partials >= 2 C floats, trust >= T floats, hyper of 8 floats");
+  TORCH_CHECK(loss_src.has_value() == loss_ring.has_value(), "lamb: loss_src and loss_ring go together");
+  if (loss_src.has_value()) {
+    CHECK_DT(*loss_src, torch::kFloat32); CHECK_DT(*loss_ring, torch::kFloat32);
+    TORCH_CHECK(loss_src->numel() == 1 && loss_ring->is_contiguous() && loss_ring->numel() >= 1,
+                "lamb: scalar loss_src, contiguous loss_ring, hyper[7] = ring slot");
+  }
+  pio::lamb_launch(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), sp, p.numel(),
+                   f32p(hyper), reinterpret_cast<const long long*>(chunk_tab.data_ptr<int64_t>()), C,
+                   tensor_tab.data_ptr<int>(), f32p(tensor_opt), (int)T, partials.data_ptr<float>(),
+                   trust.data_ptr<float>(), (float)eps, (float)clip, (float)gscale, zero_grad ? 1 : 0,
+                   loss_src.has_value() ? f32p(*loss_src) : nullptr,
+                   loss_ring.has_value() ? loss_ring->data_ptr<float>() : nullptr,
+                   loss_ring.has_value() ? (int)loss_ring->numel() : 1,
+                   clip > 0 ? f32p(*norm_part) : nullptr, stream());
+}
+
 // self-test of the device cross-lane reductions: (6, 64) = wave_sum, wave_max, half_sum,
 // half_max, xor16_sum, xor32_sum of a 64-element fp32 vector
 Tensor reduce_probe(Tensor x) {
@@ -2124,6 +2178,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("eps"), py::arg("wd"), py::arg("clip"), py::arg("gscale"), py::arg("l2") = false,
         py::arg("zero_grad") = false, py::arg("loss_src") = py::none(), py::arg("loss_ring") = py::none(),
         py::arg("norm_part") = py::none());
+  m.def("lamb", &lamb, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("shadow"), py::arg("hyper"),
+        py::arg("chunk_tab"), py::arg("tensor_tab"), py::arg("tensor_opt"), py::arg("partials"), py::arg("trust"),
+        py::arg("eps"), py::arg("clip"), py::arg("gscale"), py::arg("zero_grad") = false,
+        py::arg("loss_src") = py::none(), py::arg("loss_ring") = py::none(), py::arg("norm_part") = py::none());
+  m.attr("LAMB_CHUNK") = pio::lamb_chunk_elems();
   m.def("cast_bf16", &cast_bf16);
   m.def("reduce_probe", &reduce_probe);
   m.def("fold_replicas", &fold_replicas);

@@ -683,6 +683,43 @@ def adamw(p, g, m, v, shadow, hyper, eps, wd, clip, gscale, l2=False, zero_grad=
         shadow.copy_(p.to(shadow.dtype))
 
 
+def lamb(p, g, m, v, shadow, hyper, chunk_tab, tensor_tab, tensor_opt, partials, trust, eps, clip, gscale,
+         zero_grad=False, loss_src=None, loss_ring=None, norm_part=None):
+    """LAMB over the flat buffers, tensor by tensor (csrc/lamb.hip; the tables of
+    ``ops.optim.lamb_tables``): u = m̂ / (sqrt(v̂) + eps) + wd·w, trust = ‖w‖ / ‖u‖ for adapted
+    tensors with non-zero norms (else 1), w ← w − lr·trust·u.  Padding between tensors belongs to
+    no chunk and is left alone.  ``partials`` is the kernels' scratch: unused here."""
+    lr, step, b1, b2 = float(hyper[0]), float(hyper[1]), float(hyper[3]), float(hyper[4])
+    if loss_src is not None:  # the step's loss into the engine's ring slot hyper[7]
+        loss_ring.view(-1)[int(float(hyper[7])) % loss_ring.numel()] = loss_src.reshape(())
+    gs = gscale
+    if clip > 0:
+        norm = math.sqrt(float(norm_part.sum())) * gscale  # norm of the mean (all-reduced sum × 1/world)
+        f = clip / (norm + 1e-6)
+        if f < 1:
+            gs *= f
+    bc1, bc2s = 1 - b1 ** step, math.sqrt(1 - b2 ** step)
+    chunks, tensors, opts = chunk_tab.tolist(), tensor_tab.tolist(), tensor_opt.tolist()
+    for t, ((first, cnt), (wd, adapt)) in enumerate(zip(tensors, opts)):
+        lo = chunks[first][0]
+        hi = lo + sum(c[1] for c in chunks[first:first + cnt])
+        w, gt, mt, vt = p[lo:hi], g[lo:hi], m[lo:hi], v[lo:hi]
+        gg = gt * gs
+        if zero_grad:
+            gt.zero_()
+        mt.mul_(b1).add_(gg, alpha=1 - b1)
+        vt.mul_(b2).addcmul_(gg, gg, value=1 - b2)
+        u = (mt / bc1) / (vt.sqrt() / bc2s + eps) + wd * w
+        tr = torch.ones((), dtype=torch.float32, device=p.device)
+        if adapt:
+            nw, nu = torch.linalg.vector_norm(w.float()), torch.linalg.vector_norm(u.float())
+            tr = torch.where((nw > 0) & (nu > 0), nw / nu, tr)
+        trust[t] = tr
+        w.sub_(u * (lr * tr))
+        if shadow is not None:
+            shadow[lo:hi].copy_(w.to(shadow.dtype))
+
+
 def fold_replicas(grad, rep):
     n = rep.shape[1]
     grad[:n] += rep.sum(0)

@@ -20,6 +20,10 @@ such as ``OneCycleLR`` drive it through ``param_groups``) with torch.optim.AdamW
 and a torch-compatible ``state_dict`` layout (``exp_avg``/``exp_avg_sq``/``step`` per
 parameter), so Lightning-layout checkpoints round-trip.  lr/betas/step live in a small
 device tensor refreshed before each step, which keeps the update capturable in a hipGraph.
+
+``Lamb`` / ``FusedLamb`` add LAMB: the flat space knows where tensors begin (``offsets``), so the
+fused update takes per-tensor trust ratios and per-tensor weight decay from chunk tables
+(``lamb_tables``, csrc/lamb.hip).
 """
 from __future__ import annotations
 
@@ -296,3 +300,141 @@ class FusedAdam(FusedAdamW):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad,
                          max_grad_norm=max_grad_norm, flat=flat)
         self.l2 = True
+
+
+LAMB_CHUNK = 4096  # elements per chunk of the LAMB tables; matches kLambChunk in csrc/lamb.hip
+
+
+def lamb_tables(offsets, numels, weight_decays, adapts, device):
+    """The device tables of the fused LAMB update (csrc/lamb.hip) for tensors at ``offsets`` of
+    a flat buffer: every tensor range cut into chunks of at most ``LAMB_CHUNK`` elements (never
+    across a tensor boundary; the padding between tensors belongs to no chunk).  Returns
+    ``chunk_tab`` (C, 3) int64 = (start, length, tensor), ``tensor_tab`` (T, 2) int32 = (first
+    chunk, chunks) and ``tensor_opt`` (T, 2) fp32 = (weight decay, adapt)."""
+    chunks, tensors = [], []
+    for t, (o, n) in enumerate(zip(offsets, numels)):
+        tensors.append((len(chunks), (n + LAMB_CHUNK - 1) // LAMB_CHUNK))
+        for s in range(0, n, LAMB_CHUNK):
+            chunks.append((o + s, min(LAMB_CHUNK, n - s), t))
+    opts = [(float(wd), 1.0 if a else 0.0) for wd, a in zip(weight_decays, adapts)]
+    return (torch.tensor(chunks, dtype=torch.int64, device=device).reshape(-1, 3),
+            torch.tensor(tensors, dtype=torch.int32, device=device).reshape(-1, 2),
+            torch.tensor(opts, dtype=torch.float32, device=device).reshape(-1, 2))
+
+
+class Lamb(torch.optim.Optimizer):
+    """LAMB (You et al. 2020, the optimizer of the Perceiver papers), parameter by parameter in
+    plain PyTorch — the ``--trainer.precision=32`` path and the reference of :class:`FusedLamb`:
+
+        m ← β1·m + (1−β1)·ĝ,  v ← β2·v + (1−β2)·ĝ²          (ĝ: the gradient after global-norm clipping)
+        u = (m / (1−β1^t)) / (sqrt(v) / sqrt(1−β2^t) + eps) + wd·w
+        w ← w − lr · trust · u,   trust = ‖w‖ / ‖u‖ when both norms are non-zero, else 1
+
+    With ``exclude_1d`` (a group option, default on) tensors with ``ndim ≤ 1`` (biases, LayerNorm
+    gains) are neither decayed nor adapted: ``wd = 0``, ``trust = 1``.  ``max_grad_norm > 0`` clips
+    the gradient of all groups together by ``max_grad_norm / (‖g‖ + 1e-6)``, as the fused
+    optimizers do."""
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-6, weight_decay: float = 0.01,
+                 exclude_1d: bool = True, max_grad_norm: float = 0.0):
+        defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, exclude_1d=bool(exclude_1d))
+        super().__init__(params, defaults)
+        self.max_grad_norm = float(max_grad_norm)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        clip = 1.0
+        if self.max_grad_norm > 0:
+            sq = [p.grad.float().pow(2).sum() for g in self.param_groups for p in g["params"] if p.grad is not None]
+            if sq:
+                f = self.max_grad_norm / (math.sqrt(float(torch.stack(sq).sum())) + 1e-6)
+                clip = min(f, 1.0)
+        for g in self.param_groups:
+            b1, b2 = g["betas"]
+            for p in g["params"]:
+                if p.grad is None:
+                    continue
+                st = self.state[p]
+                if not st:
+                    st["step"] = 0
+                    st["exp_avg"] = torch.zeros_like(p)
+                    st["exp_avg_sq"] = torch.zeros_like(p)
+                st["step"] += 1
+                grad = p.grad * clip
+                m, v = st["exp_avg"], st["exp_avg_sq"]
+                m.mul_(b1).add_(grad, alpha=1 - b1)
+                v.mul_(b2).addcmul_(grad, grad, value=1 - b2)
+                bc1, bc2 = 1 - b1 ** st["step"], 1 - b2 ** st["step"]
+                plain = g["exclude_1d"] and p.dim() <= 1
+                u = (m / bc1) / (v.sqrt() / math.sqrt(bc2) + g["eps"])
+                if not plain and g["weight_decay"]:
+                    u = u + g["weight_decay"] * p
+                trust = 1.0
+                if not plain:
+                    nw, nu = float(torch.linalg.vector_norm(p)), float(torch.linalg.vector_norm(u))
+                    if nw > 0 and nu > 0:
+                        trust = nw / nu
+                p.sub_(u, alpha=g["lr"] * trust)
+        return loss
+
+
+class FusedLamb(FusedAdamW):
+    """:class:`Lamb` over a :class:`FlatParameterSpace` (one parameter group): two streaming HIP
+    kernels and a per-tensor reduction over chunk tables of the flat buffer (csrc/lamb.hip), or
+    their emulation on the CPU.  A ``FusedAdamW`` to the step engine (captured update, loss ring,
+    gradient cleared as it is consumed, ``grad_scale``), with an AdamW-layout ``state_dict``.  The
+    trust ratios need whole tensors, so there are no per-bucket or range updates."""
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-6, weight_decay: float = 0.01,
+                 exclude_1d: bool = True, max_grad_norm: float = 0.0, flat: Optional[FlatParameterSpace] = None):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
+                         flat=flat)
+        self.param_groups[0]["exclude_1d"] = bool(exclude_1d)
+        f = self.flat
+        wds, adapts = self._tensor_options()
+        self.chunk_tab, self.tensor_tab, self.tensor_opt = lamb_tables(
+            f.offsets, [p.numel() for p in f.params], wds, adapts, f.device)
+        # per-chunk (Σw², Σu²) of pass 1, and the per-tensor trust ratios of the last update
+        self.partials = torch.zeros(2 * self.chunk_tab.shape[0], dtype=torch.float32, device=f.device)
+        self.trust = torch.ones(len(f.params), dtype=torch.float32, device=f.device)
+
+    def _tensor_options(self):
+        g = self.param_groups[0]
+        plain = [g["exclude_1d"] and p.dim() <= 1 for p in self.flat.params]
+        return [0.0 if pl else g["weight_decay"] for pl in plain], [not pl for pl in plain]
+
+    def last_trust(self) -> torch.Tensor:
+        """(T,) fp32: the trust ratio every tensor of ``flat.params`` took in the last update."""
+        return self.trust
+
+    def bucket_updates_ok(self) -> bool:
+        return False
+
+    def range_update(self, lo: int, hi: int):
+        raise NotImplementedError("FusedLamb updates whole tensors (per-tensor trust ratios): no range updates")
+
+    def device_update(self, zero_grad: bool = False, norm_staged: bool = False):
+        """The capturable part: fold, (grad-norm), then the LAMB launches over the flat buffers."""
+        f = self.flat
+        K = ext.require() if f.device.type == "cuda" else emulation
+        f.fold()
+        if self.max_grad_norm > 0:
+            K.sumsq(f.grad, self.norm_part)
+        lo = self.loss_out
+        K.lamb(f.data, f.grad, self.exp_avg, self.exp_avg_sq, f.shadow, self.hyper, self.chunk_tab, self.tensor_tab,
+               self.tensor_opt, self.partials, self.trust, self.param_groups[0]["eps"], self.max_grad_norm,
+               self.grad_scale, zero_grad=zero_grad and f.grad_rep is None,
+               loss_src=None if lo is None else lo[0], loss_ring=None if lo is None else lo[1],
+               norm_part=self.norm_part)
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        # weight_decay / exclude_1d may have come with the groups: refresh the table in place
+        # (captured graphs read this very tensor)
+        wds, adapts = self._tensor_options()
+        self.tensor_opt.copy_(torch.tensor([(wd, 1.0 if a else 0.0) for wd, a in zip(wds, adapts)],
+                                           dtype=torch.float32).reshape(-1, 2))

@@ -280,6 +280,26 @@ class Trainer:
                     warnings.warn("scheduler could not be re-bound to the fused optimizer; dropped")
                     sched = None
             opt = new
+        elif self.fused and type(opt).__name__ == "Lamb":
+            from ..ops.optim import FusedLamb
+
+            g = opt.param_groups[0]
+            if len(opt.param_groups) > 1:
+                warnings.warn("the fused LAMB takes the first parameter group's options for every parameter")
+            new = FusedLamb([p for p in model.parameters() if p.requires_grad], lr=g["lr"], betas=g["betas"],
+                            eps=g["eps"], weight_decay=g.get("weight_decay", 0.0),
+                            exclude_1d=g.get("exclude_1d", True),
+                            max_grad_norm=self.gradient_clip_val or getattr(opt, "max_grad_norm", 0.0))
+            if sched is not None:
+                init = getattr(model.hparams, "get", lambda *_: None)("scheduler_init")
+                if init is not None:
+                    from .module import instantiate_class
+
+                    sched = instantiate_class(new, init)
+                else:
+                    warnings.warn("scheduler could not be re-bound to the fused optimizer; dropped")
+                    sched = None
+            opt = new
         return opt, sched
 
     def _attach(self, model, datamodule):
