@@ -126,6 +126,15 @@ unsigned check_errors_mlm_head(bool);
 unsigned check_errors_ce_head(bool);
 unsigned check_errors_topk_head(bool);
 unsigned check_errors_rowgemm(bool);
+unsigned check_errors_soft_ce_head(bool);
+int soft_ce_row_tiles(int);
+void soft_ce_fwd_launch(int, const float*, const uint16_t*, const float*, const int64_t*, const int64_t*, const float*,
+                        float, int, int, float*, int*, uint16_t*, float*, float*, float*, hipStream_t);
+void soft_ce_bwd_launch(int, const uint16_t*, const uint16_t*, const float*, const int64_t*, const int64_t*,
+                        const float*, float, const float*, const float*, const float*, int, int, float*, float*, float*,
+                        int, hipStream_t);
+void batch_mix_launch(const float*, const int64_t*, const float*, float*, int64_t*, float*, int, int, int, int,
+                      hipStream_t);
 void embed_bwd_launch(const int64_t*, const float*, float*, float*, int, int, int, float, hipStream_t);
 void embed_bwd_sorted_launch(const int64_t*, const int64_t*, const float*, float*, long long, int, float, hipStream_t);
 bool embed_bwd_local_launch(const int64_t*, const float*, float*, float*, int, int, int, float, const SlabJob&,
@@ -191,7 +200,8 @@ hipStream_t stream() { return at::hip::getCurrentHIPStream(); }
 int64_t check_errors(bool reset) {
   return (int64_t)(pio::check_errors_elementwise(reset) | pio::check_errors_mlm_head(reset) |
                    pio::check_errors_ce_head(reset) | pio::check_errors_topk_head(reset) |
-                   pio::check_errors_rowgemm(reset) | pio::check_errors_pixel_head(reset));
+                   pio::check_errors_rowgemm(reset) | pio::check_errors_pixel_head(reset) |
+                   pio::check_errors_soft_ce_head(reset));
 }
 bool checked_build() { return PIO_CHECKS != 0; }
 // checked builds, outside graph capture: wait for the kernel just launched and raise on any
@@ -1380,6 +1390,80 @@ std::vector<Tensor> vocab_topk(Tensor h, OptT idx, Tensor w, Tensor bias, int64_
   return {values, indices, lse};
 }
 
+// Soft-target classifier head (soft_ce_head.hip): rows h (M, C) fp32, two labels and a weight per
+// row, label smoothing eps.  → {loss (mean over the rows whose label_a is not -100), lse (M,),
+// pred (M,) int32 argmax of the logits (lower class on a tie), the compact bf16 rows, count (1,)}.
+// C ∈ {64, 128}, 1 ≤ V ≤ 1024.
+void soft_ce_check(const Tensor& la, const Tensor& lb, const Tensor& lam, const Tensor& w, const Tensor& bias, int M,
+                   int C, double eps) {
+  CHECK_DT(la, torch::kInt64); CHECK_DT(lb, torch::kInt64); CHECK_DT(lam, torch::kFloat32);
+  TORCH_CHECK(la.is_contiguous() && lb.is_contiguous() && lam.is_contiguous() && w.is_contiguous() &&
+              bias.is_contiguous(), "soft_ce: operands must be contiguous");
+  TORCH_CHECK(la.numel() == M && lb.numel() == M && lam.numel() == M, "soft_ce: one label pair and weight per row");
+  const int64_t V = w.size(0);
+  TORCH_CHECK(w.dim() == 2 && w.size(1) == C && bias.numel() == V && (C == 64 || C == 128) && V >= 1 && V <= 1024,
+              "soft_ce: supported head shapes are C in {64, 128}, 1 <= V <= 1024");
+  TORCH_CHECK(M >= 1 && eps >= 0.0 && eps < 1.0, "soft_ce: needs M >= 1 and eps in [0, 1)");
+  for (const Tensor* t : {&la, &lb, &lam, &w, &bias}) CHECK_CUDA(*t);
+}
+
+std::vector<Tensor> soft_ce_fwd(Tensor h, Tensor la, Tensor lb, Tensor lam, Tensor w, Tensor bias, double eps) {
+  CHECK_CUDA(h);
+  CHECK_DT(h, torch::kFloat32);
+  TORCH_CHECK(h.dim() == 2 && h.is_contiguous() && h.size(0) < (1 << 24), "soft_ce_fwd: h must be (M, C) contiguous");
+  const int M = (int)h.size(0), C = (int)h.size(1), V = (int)w.size(0);
+  soft_ce_check(la, lb, lam, w, bias, M, C, eps);
+  auto f32 = h.options().dtype(torch::kFloat32);
+  const int nrt = pio::soft_ce_row_tiles(M);
+  Tensor loss = torch::empty({}, f32), lse = torch::empty({M}, f32), count = torch::empty({1}, f32);
+  Tensor pred = torch::empty({M}, f32.dtype(torch::kInt32)), hs = torch::empty({M, C}, f32.dtype(torch::kBFloat16));
+  Tensor blk = torch::empty({2 * nrt}, f32);
+  pio::soft_ce_fwd_launch(C, h.data_ptr<float>(), bfp(w), f32p(bias), la.data_ptr<int64_t>(), lb.data_ptr<int64_t>(),
+                          f32p(lam), (float)eps, M, V, lse.data_ptr<float>(), pred.data_ptr<int>(), bfp_mut(hs),
+                          blk.data_ptr<float>(), loss.data_ptr<float>(), count.data_ptr<float>(), stream());
+  checked_sync("soft_ce_fwd");
+  return {loss, lse, pred, hs, count};
+}
+
+// hs: the compact bf16 rows of soft_ce_fwd.  dH (M, C) is overwritten; dW / db are added to
+// (accumulate) or overwritten.
+void soft_ce_bwd(Tensor hs, Tensor la, Tensor lb, Tensor lam, Tensor w, Tensor bias, double eps, Tensor lse, Tensor gout,
+                 Tensor count, Tensor dH, Tensor dW, Tensor db, bool accumulate) {
+  CHECK_CUDA(hs);
+  TORCH_CHECK(hs.dim() == 2 && hs.is_contiguous(), "soft_ce_bwd: hs must be the compact (M, C) bf16 rows");
+  const int M = (int)hs.size(0), C = (int)hs.size(1), V = (int)w.size(0);
+  soft_ce_check(la, lb, lam, w, bias, M, C, eps);
+  for (const Tensor* t : {&lse, &gout, &count, &dH, &dW, &db}) {
+    CHECK_CUDA(*t); CHECK_DT(*t, torch::kFloat32);
+    TORCH_CHECK(t->is_contiguous(), "soft_ce_bwd: operands must be contiguous");
+  }
+  TORCH_CHECK(lse.numel() == M && gout.numel() >= 1 && count.numel() >= 1, "soft_ce_bwd: bad lse / gout / count");
+  TORCH_CHECK(dH.numel() == (int64_t)M * C && dW.numel() == (int64_t)V * C && db.numel() == V,
+              "soft_ce_bwd: dH (M, C), dW (V, C), db (V,)");
+  pio::soft_ce_bwd_launch(C, bfp(hs), bfp(w), f32p(bias), la.data_ptr<int64_t>(), lb.data_ptr<int64_t>(), f32p(lam),
+                          (float)eps, f32p(lse), f32p(gout), f32p(count), M, V, dH.data_ptr<float>(),
+                          dW.data_ptr<float>(), db.data_ptr<float>(), accumulate ? 1 : 0, stream());
+}
+
+// MixUp / CutMix of a channels-last batch with its flipped self; mix = {mode, lambda, y0, y1, x0, x1}
+// as fp32 words on the device (read by the kernel).  → {mixed x, label_b, lam (B,)}
+std::vector<Tensor> batch_mix(Tensor x, Tensor y, Tensor mix) {
+  CHECK_CUDA(x); CHECK_CUDA(y); CHECK_CUDA(mix);
+  CHECK_DT(x, torch::kFloat32); CHECK_DT(y, torch::kInt64); CHECK_DT(mix, torch::kFloat32);
+  TORCH_CHECK(x.dim() == 4 && x.is_contiguous() && y.is_contiguous() && mix.is_contiguous(),
+              "batch_mix: x must be (B, H, W, Ch) contiguous");
+  TORCH_CHECK(y.numel() == x.size(0) && mix.numel() >= 6 && x.size(0) >= 1, "batch_mix: y (B,), mix (6,)");
+  const int64_t n = x.size(1) * x.size(2) * x.size(3);
+  TORCH_CHECK(n >= 1 && n < ((int64_t)1 << 30) && x.size(0) < (1 << 16), "batch_mix: sample too large");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0, "batch_mix: x must be 16-byte aligned");
+  Tensor out = torch::empty_like(x), yb = torch::empty_like(y);
+  Tensor lam = torch::empty({x.size(0)}, x.options());
+  pio::batch_mix_launch(x.data_ptr<float>(), y.data_ptr<int64_t>(), f32p(mix), out.data_ptr<float>(),
+                        yb.data_ptr<int64_t>(), lam.data_ptr<float>(), (int)x.size(0), (int)x.size(1), (int)x.size(2),
+                        (int)x.size(3), stream());
+  return {out, yb, lam};
+}
+
 Tensor embed_fwd(Tensor ids, Tensor E, Tensor P, double scale) {
   TORCH_CHECK(ids.is_contiguous() && E.is_contiguous() && P.is_contiguous());
   CHECK_DT(ids, torch::kInt64);
@@ -2167,6 +2251,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("accumulate"), py::arg("rowmap") = py::none(), py::arg("slab") = false, py::arg("u") = py::none(),
         py::arg("u_ml") = py::none());
   m.def("vocab_topk", &vocab_topk, py::arg("h"), py::arg("idx"), py::arg("w"), py::arg("bias"), py::arg("k"));
+  m.def("soft_ce_fwd", &soft_ce_fwd, py::arg("h"), py::arg("label_a"), py::arg("label_b"), py::arg("lam"), py::arg("w"),
+        py::arg("bias"), py::arg("eps"));
+  m.def("soft_ce_bwd", &soft_ce_bwd, py::arg("hs"), py::arg("label_a"), py::arg("label_b"), py::arg("lam"), py::arg("w"),
+        py::arg("bias"), py::arg("eps"), py::arg("lse"), py::arg("gout"), py::arg("count"), py::arg("dH"), py::arg("dW"),
+        py::arg("db"), py::arg("accumulate"));
+  m.def("batch_mix", &batch_mix, py::arg("x"), py::arg("y"), py::arg("mix"));
   m.def("embed_fwd", &embed_fwd);
   m.def("embed_bwd", &embed_bwd, py::arg("ids"), py::arg("g"), py::arg("dE"), py::arg("dP"), py::arg("scale"),
         py::arg("job_slab") = py::none(), py::arg("job_dsts") = std::vector<Tensor>(),

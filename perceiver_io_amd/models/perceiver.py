@@ -135,6 +135,12 @@ class PerceiverDecoder(nn.Module):
         adapters); on the GPU through the fused vocab-projection + CE kernels (no logits tensor)."""
         return ops.mlm_head.classification_loss(self, x_latent, labels)
 
+    def soft_loss(self, x_latent, label_a, label_b, lam, label_smoothing: float = 0.0):
+        """→ (loss, pred): mean cross-entropy against the soft targets
+        ``(1 − ε)·(λ·e_a + (1 − λ)·e_b) + ε/V`` and the argmax class of every row; on the GPU the
+        fused soft-target head (no logits tensor)."""
+        return ops.mlm_head.soft_classification_loss(self, x_latent, label_a, label_b, lam, label_smoothing)
+
     def hidden_at(self, x, idx):
         """Decoder output at output-query rows ``idx`` (B, K') only, ``(B, K', C_out)``: queries
         never interact, so this equals ``hidden(x)`` gathered at ``idx``.  The gather's backward
@@ -167,6 +173,25 @@ class PerceiverIO(Sequential):
         try:
             x_latent, _ = self.encoder(x, pad_mask)
             return self.decoder.loss(x_latent, labels)
+        finally:
+            look["want_kv"] = look["have_q"] = None
+
+    def soft_loss(self, x, label_a, label_b=None, lam=None, label_smoothing: float = 0.0, pad_mask=None):
+        """Training loss of a classifier against MixUp / CutMix label pairs with label smoothing:
+        → (loss, pred).  Sample i's target is ``(1 − ε)·(λ_i·e_a + (1 − λ_i)·e_b) + ε/V``;
+        ``label_b=None`` and ``lam=None`` mean hard labels (λ = 1).  ``pred`` is the argmax class
+        of every sample; the encoder and the decoder run as in :meth:`loss`."""
+        if label_b is None:
+            label_b = label_a
+        if lam is None:
+            lam = torch.ones(label_a.shape[0], device=label_a.device, dtype=torch.float32)
+        look = ops.fused._LOOKAHEAD
+        look["want_kv"] = (ops.fused.decoder_kv_lookahead(
+            self.decoder.cross_attention, sample_block=True,
+            backward=not ready_point_armed(self.decoder, "decoder")) if ops.use_hip(x) else None)
+        try:
+            x_latent, _ = self.encoder(x, pad_mask)
+            return self.decoder.soft_loss(x_latent, label_a, label_b, lam, label_smoothing)
         finally:
             look["want_kv"] = look["have_q"] = None
 

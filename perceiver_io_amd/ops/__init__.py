@@ -102,4 +102,25 @@ def use_hip(t: torch.Tensor) -> bool:
     return True
 
 
+MIX_OFF, MIX_MIXUP, MIX_CUTMIX = 0, 1, 2
+
+
+def batch_mix(x: torch.Tensor, y: torch.Tensor, mix: torch.Tensor):
+    """MixUp / CutMix of a channels-last image batch ``x`` (B, H, W, Ch) with its flipped self
+    (sample i pairs with sample B − 1 − i) → ``(mixed, label_b, lam)``; ``x`` is not modified.
+    ``mix`` holds the fp32 words ``{mode, λ, y0, y1, x0, x1}`` (mode 0 off, 1 MixUp, 2 CutMix with
+    the partner's pixels inside rows [y0, y1) × columns [x0, x1)) on ``x``'s device.  HIP path:
+    one kernel that reads ``mix`` from device memory (``csrc/soft_ce_head.hip``) — no host sync,
+    and a replayed hipGraph mixes with whatever words were staged for that step."""
+    y = y if y.dtype == torch.int64 and y.is_contiguous() else y.to(torch.int64).contiguous()
+    if use_hip(x):
+        xc = x if x.dtype == torch.float32 and x.is_contiguous() else x.float().contiguous()
+        m = mix.to(device=x.device, dtype=torch.float32).contiguous()
+        out, yb, lam = ext.require().batch_mix(xc, y, m)
+        return out, yb, lam
+    from . import emulation
+
+    return emulation.batch_mix(x, y, mix)
+
+
 from . import attention, fused, masking, mlm_head, optim  # noqa: E402,F401

@@ -608,6 +608,81 @@ def ce_bwd(h, labels, w, bias, lse, gout, count, dH, dW, db, accumulate, rowmap=
     return None
 
 
+def _soft_targets(label_a, label_b, lam, eps, V):
+    """→ (valid (M,) bool, t (M, V) fp32): t = (1 − ε)·(λ·e_a + (1 − λ)·e_b) + ε/V on the rows whose
+    labels are both inside [0, V) (``label_a == -100``: no loss), zero elsewhere."""
+    valid = (label_a >= 0) & (label_a < V) & (label_b >= 0) & (label_b < V)
+    lam = lam.float()[:, None]
+    ea = F.one_hot(torch.where(valid, label_a, torch.zeros_like(label_a)), V).float()
+    eb = F.one_hot(torch.where(valid, label_b, torch.zeros_like(label_b)), V).float()
+    t = (1.0 - eps) * (lam * ea + (1.0 - lam) * eb) + eps / V
+    return valid, t * valid[:, None].float()
+
+
+def soft_ce_fwd(h, label_a, label_b, lam, w, bias, eps):
+    """Soft-target head forward (csrc/soft_ce_head.hip) → (mean loss over the labelled rows as a
+    0-dim tensor, lse (M,), pred (M,) int32 = argmax of the logits with the lower class on a tie,
+    the compact bf16 rows, count (1,))."""
+    logits = _bf(h.float()) @ _bf(w.float()).t() + bias.float()
+    V = logits.shape[1]
+    lse = torch.logsumexp(logits, -1)
+    valid, t = _soft_targets(label_a, label_b, lam, eps, V)
+    rows = torch.where(valid, lse - (t * logits).sum(-1), torch.zeros_like(lse))
+    count = valid.sum().to(torch.float32).reshape(1)
+    mx = logits.max(-1, keepdim=True).values
+    ar = torch.arange(V, device=logits.device).expand_as(logits)
+    pred = torch.where(logits == mx, ar, torch.full_like(ar, V)).min(-1).values.to(torch.int32)
+    return rows.sum() / count.reshape(()).clamp(min=1), lse, pred, h.to(torch.bfloat16).contiguous(), count
+
+
+def soft_ce_bwd(hs, label_a, label_b, lam, w, bias, eps, lse, gout, count, dH, dW, db, accumulate):
+    """dz = g / max(count, 1)·(softmax(z) − t) on the labelled rows, a bf16 pair hi + lo as a GEMM
+    operand (the kernel's two MFMAs); dH is overwritten, dW / db are added to (``accumulate``) or
+    overwritten."""
+    gscale = gout.reshape(-1)[0] / count.reshape(-1)[0].clamp(min=1)
+    logits = _bf(hs.float()) @ _bf(w.float()).t() + bias.float()
+    valid, t = _soft_targets(label_a, label_b, lam, eps, logits.shape[1])
+    p = torch.exp(logits - lse[:, None]) * valid[:, None].float()
+    dz = (p - t) * gscale
+    dz2 = _bf(dz) + _bf(dz - _bf(dz))
+    dH.copy_((dz2 @ _bf(w.float())).view_as(dH))
+    gw = dz2.t() @ _bf(hs.float())
+    gb = dz.sum(0)
+    if accumulate:
+        dW.add_(gw.view_as(dW))
+        db.add_(gb)
+    else:
+        dW.copy_(gw.view_as(dW))
+        db.copy_(gb)
+    return None
+
+
+def batch_mix(x, y, mix):
+    """MixUp / CutMix of a channels-last batch ``x`` (B, H, W, Ch) with its flipped self (sample i
+    pairs with B − 1 − i; the middle sample of an odd batch stays as it is).  ``mix`` holds the
+    fp32 words {mode, λ, y0, y1, x0, x1}: mode 0 off, 1 MixUp ``λ·x_i + (1 − λ)·x_j``, 2 CutMix
+    (rows y0 ≤ y < y1, columns x0 ≤ x < x1 come from the partner).  → (mixed, label_b, lam (B,));
+    ``x`` is not modified."""
+    m = [float(v) for v in mix.detach().reshape(-1)[:6].tolist()]
+    mode = int(m[0]) if int(m[0]) in (1, 2) else 0
+    B, H, W = x.shape[0], x.shape[1], x.shape[2]
+    if mode == 0:
+        return x.clone(), y.clone(), torch.ones(B, dtype=torch.float32, device=x.device)
+    lam = torch.tensor(m[1], dtype=torch.float32, device=x.device)
+    xf = x.flip(0)
+    if mode == 1:
+        out = lam * x + (1.0 - lam) * xf
+        if B % 2:
+            out[B // 2] = x[B // 2]
+    else:
+        y0, y1, x0, x1 = (int(v) for v in m[2:6])
+        ys = torch.arange(H, device=x.device)[:, None]
+        xs = torch.arange(W, device=x.device)[None, :]
+        box = (ys >= y0) & (ys < y1) & (xs >= x0) & (xs < x1)
+        out = torch.where(box[None, :, :, None], xf, x)
+    return out, y.flip(0).contiguous(), lam.expand(B).contiguous()
+
+
 def embed_fwd(ids, E, P, scale):
     return E[ids] * scale + P[: ids.shape[1]].unsqueeze(0)
 

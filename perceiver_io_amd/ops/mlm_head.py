@@ -374,3 +374,85 @@ def classification_loss(decoder, x_latent: torch.Tensor, labels: torch.Tensor):
         return _MaskedCE.apply(h, lin.weight, lin.bias, None, lab, None)  # count: rows with a label, in-kernel
     return F.cross_entropy(ad(h).float(), labels)
 
+
+# ------------------------------------------------------------------------------------------
+# soft targets: MixUp / CutMix label pairs and label smoothing
+# ------------------------------------------------------------------------------------------
+SOFT_CE_MAX_V = 1024  # csrc/soft_ce_head.hip recomputes the logit tiles in its backward: classifier-sized V only
+
+
+class _SoftCE(torch.autograd.Function):
+    """Mean over the labelled rows of ``cross_entropy(h·wᵀ + bias, t)`` with
+    ``t = (1 − ε)·(λ·e_a + (1 − λ)·e_b) + ε/V`` → (loss, pred): ``csrc/soft_ce_head.hip``.  The
+    backward writes dH and adds dW / db straight into ``.grad`` (flat-buffer views); neither pass
+    uses atomics, so the outputs are bitwise repeatable."""
+
+    @staticmethod
+    def forward(ctx, h, weight, bias, label_a, label_b, lam, eps):
+        from .fused import kernels, weight_cache
+
+        c = h.shape[-1]
+        h2 = h.reshape(-1, c)
+        if h2.dtype != torch.float32 or not h2.is_contiguous():
+            h2 = h2.float().contiguous()
+        wb = weight_cache.get(weight)  # bf16 shadow written by the fused optimizer
+        K = kernels(h2)
+        loss, lse, pred, hs, cnt = K.soft_ce_fwd(h2, label_a, label_b, lam, wb, bias.detach().contiguous(), float(eps))
+        ctx.save_for_backward(hs, wb, lse, label_a, label_b, lam, cnt)
+        ctx.hshape, ctx.eps, ctx.K = h.shape, float(eps), K
+        ctx.weight, ctx.bias_p = weight, bias
+        ctx.mark_non_differentiable(pred)
+        return loss, pred
+
+    @staticmethod
+    def backward(ctx, g, _gpred):
+        hs, wb, lse, label_a, label_b, lam, cnt = ctx.saved_tensors
+        gout = g.reshape(1)
+        if gout.dtype != torch.float32:
+            gout = gout.to(torch.float32)
+        for p in (ctx.weight, ctx.bias_p):
+            if p.grad is None:
+                p.grad = torch.zeros_like(p)
+        dh = torch.empty(hs.shape, device=hs.device, dtype=torch.float32)
+        ctx.K.soft_ce_bwd(hs, label_a, label_b, lam, wb, ctx.bias_p.detach().contiguous(), ctx.eps, lse,
+                          gout.contiguous(), cnt, dh, ctx.weight.grad, ctx.bias_p.grad, True)
+        return dh.view(ctx.hshape), None, None, None, None, None, None
+
+
+def soft_targets(label_a, label_b, lam, eps: float, num_classes: int):
+    """→ (valid (M,) bool, t (M, V)): ``(1 − ε)·(λ·e_a + (1 − λ)·e_b) + ε/V``; rows with
+    ``label_a == -100`` carry no loss (their row of ``t`` is a placeholder)."""
+    valid = label_a != -100
+    a = torch.where(valid, label_a, torch.zeros_like(label_a))
+    b = torch.where(valid, label_b, torch.zeros_like(label_b))
+    lam = lam.float()[:, None]
+    t = (1.0 - eps) * (lam * F.one_hot(a, num_classes).float() + (1.0 - lam) * F.one_hot(b, num_classes).float())
+    return valid, t + eps / num_classes
+
+
+def soft_classification_loss(decoder, x_latent: torch.Tensor, label_a: torch.Tensor, label_b: torch.Tensor,
+                             lam: torch.Tensor, eps: float = 0.0):
+    """→ (loss, pred) of a one-query classification decoder against the soft targets
+    ``(1 − ε)·(λ·e_a + (1 − λ)·e_b) + ε/V`` (MixUp / CutMix label pairs, label smoothing ε): the mean
+    ``cross_entropy`` over the rows whose ``label_a`` is not ``-100`` and the argmax class of every
+    row.  Same dispatch rule as :func:`classification_loss`: on the HIP path (C ∈ {64, 128},
+    V ≤ 1024) the fused soft-target head, no logits tensor; otherwise ``F.cross_entropy`` with
+    probability targets and ``argmax`` on the adapter's logits."""
+    from . import use_hip
+
+    h = decoder.hidden(x_latent)
+    ad = decoder.output_adapter
+    lin = getattr(ad, "linear", None)
+    i64 = lambda t: t if t.dtype == torch.int64 and t.is_contiguous() else t.to(torch.int64).contiguous()  # noqa: E731
+    label_a, label_b = i64(label_a), i64(label_b)
+    lam = lam if lam.dtype == torch.float32 and lam.is_contiguous() else lam.float().contiguous()
+    if (lin is not None and lin.bias is not None and use_hip(h) and h.dim() == 3 and h.shape[1] == 1
+            and h.shape[-1] in (64, 128) and 1 <= lin.weight.shape[0] <= SOFT_CE_MAX_V
+            and label_a.dim() == 1 and label_a.shape[0] == h.shape[0]):
+        return _SoftCE.apply(h, lin.weight, lin.bias, label_a, label_b, lam, float(eps))
+    logits = ad(h).float()
+    valid, t = soft_targets(label_a, label_b, lam, eps, logits.shape[-1])
+    rows = F.cross_entropy(logits, t, reduction="none")
+    loss = (rows * valid.float()).sum() / valid.sum().clamp(min=1)
+    return loss, logits.argmax(dim=-1)
+

@@ -92,16 +92,40 @@ class Accuracy:
 
 
 class LitClassifier(LitModel):
-    def __init__(self, *args: Any, **kwargs: Any):
+    def __init__(self, *args: Any, label_smoothing: float = 0.0, **kwargs: Any):
         super().__init__(*args, **kwargs)
         self.loss = nn.CrossEntropyLoss()
         self.acc = Accuracy()
 
+    @property
+    def soft_targets(self) -> bool:
+        """True when the step runs through the soft-target head (label smoothing; subclasses add
+        their mixing options).  False: ``step`` is the plain hard-label step."""
+        return float(self.hparams.get("label_smoothing", 0.0) or 0.0) != 0.0
+
     def step(self, batch):
+        if self.soft_targets:
+            return self.soft_step(batch)
         logits, y = self(batch)
         loss = self.loss(logits.float(), y)
         acc = self.acc(logits.argmax(dim=-1), y)
         return loss, acc
+
+    def soft_inputs(self, batch):
+        """→ (x, pad_mask, label_a, label_b, lam) of a batch for the soft-target step;
+        ``label_b`` / ``lam`` None: hard labels."""
+        raise NotImplementedError
+
+    def soft_step(self, batch):
+        """Loss and accuracy through ``PerceiverIO.soft_loss`` (fused soft-target head on the GPU,
+        no logits tensor): ``nn.CrossEntropyLoss(label_smoothing)`` semantics on hard labels, the
+        label pair's mixture when a subclass mixed the batch.  Accuracy compares the head's
+        argmax with the dominant label (``a`` if λ ≥ 0.5, else ``b``)."""
+        x, pad_mask, a, b, lam = self.soft_inputs(batch)
+        loss, pred = self.model.soft_loss(x, a, b, lam, label_smoothing=float(self.hparams.get("label_smoothing", 0.0)),
+                                          pad_mask=pad_mask)
+        y = a if b is None else torch.where(lam >= 0.5, a, b)
+        return loss, self.acc(pred, y)
 
     def training_step(self, batch, batch_idx):
         loss, acc = self.step(batch)
@@ -120,11 +144,42 @@ class LitClassifier(LitModel):
         self.log("test_acc", acc)
 
 
+def draw_mix(rng, image_hw: Tuple[int, int], mixup_alpha: float = 0.0, cutmix_alpha: float = 0.0,
+             mix_prob: float = 1.0, mix_switch_prob: float = 0.5):
+    """One batch-mode MixUp / CutMix draw (timm ``Mixup`` semantics, ``mode="batch"``) from the
+    ``numpy.random.Generator`` ``rng`` → the six words ``[mode, λ, y0, y1, x0, x1]`` of
+    ``ops.batch_mix``.  With probability ``mix_prob`` the batch is mixed; CutMix is chosen with
+    probability ``mix_switch_prob`` when both alphas are > 0; λ ~ Beta(α, α); the CutMix box has
+    side ratio √(1 − λ) around a uniform centre, is clipped to the image, and λ is reset to
+    ``1 − box_area / (H·W)``."""
+    off = [0.0, 1.0, 0.0, 0.0, 0.0, 0.0]
+    if (mixup_alpha <= 0.0 and cutmix_alpha <= 0.0) or rng.random() >= mix_prob:
+        return off
+    if mixup_alpha > 0.0 and cutmix_alpha > 0.0:
+        cut = bool(rng.random() < mix_switch_prob)
+    else:
+        cut = cutmix_alpha > 0.0
+    alpha = cutmix_alpha if cut else mixup_alpha
+    lam = float(rng.beta(alpha, alpha))
+    if not cut:
+        return [1.0, lam, 0.0, 0.0, 0.0, 0.0]
+    H, W = int(image_hw[0]), int(image_hw[1])
+    ratio = (1.0 - lam) ** 0.5
+    ch, cw = int(H * ratio), int(W * ratio)
+    cy, cx = int(rng.integers(0, H)), int(rng.integers(0, W))
+    y0, y1 = min(max(cy - ch // 2, 0), H), min(max(cy + ch // 2, 0), H)
+    x0, x1 = min(max(cx - cw // 2, 0), W), min(max(cx + cw // 2, 0), W)
+    lam = 1.0 - ((y1 - y0) * (x1 - x0)) / float(H * W)
+    return [2.0, lam, float(y0), float(y1), float(x0), float(x1)]
+
+
 class LitImageClassifier(LitClassifier):
     def __init__(self, image_shape: Tuple[int, int, int], num_classes: int, *args: Any, num_frequency_bands: int = 32,
-                 **kwargs: Any):
+                 mixup_alpha: float = 0.0, cutmix_alpha: float = 0.0, mix_prob: float = 1.0,
+                 mix_switch_prob: float = 0.5, **kwargs: Any):
         super().__init__(*args, **kwargs)
         self.model = self.create_model()
+        self._mix_rng = None
 
     def create_model(self):
         hp = self.hparams
@@ -140,8 +195,53 @@ class LitImageClassifier(LitClassifier):
         return PerceiverIO(encoder, decoder)
 
     def forward(self, batch):
-        x, y = batch
+        x, y = batch[0], batch[1]
         return self.model(x), y
+
+    # -- MixUp / CutMix ------------------------------------------------------------------------
+    @property
+    def mixing(self) -> bool:
+        hp = self.hparams
+        return float(hp.get("mixup_alpha", 0.0) or 0.0) > 0.0 or float(hp.get("cutmix_alpha", 0.0) or 0.0) > 0.0
+
+    @property
+    def soft_targets(self) -> bool:
+        return super().soft_targets or self.mixing
+
+    def draw_mix(self) -> torch.Tensor:
+        """This micro-batch's mix words as a host tensor: one draw from the module's own
+        ``numpy.random.Generator``, seeded from the trainer seed (rank-shifted) on first use."""
+        if self._mix_rng is None:
+            import numpy as np
+
+            tr = self._trainer
+            seed = getattr(tr, "seed", None) if tr is not None else None
+            rank = getattr(getattr(tr, "dist", None), "rank", 0) if tr is not None else 0
+            base = int(seed) if seed is not None else int(torch.initial_seed() % (1 << 31))
+            self._mix_rng = np.random.default_rng([base, int(rank), 0x4D4958])
+        hp = self.hparams
+        return torch.tensor(draw_mix(self._mix_rng, tuple(hp.image_shape)[:2], float(hp.get("mixup_alpha", 0.0)),
+                                     float(hp.get("cutmix_alpha", 0.0)), float(hp.get("mix_prob", 1.0)),
+                                     float(hp.get("mix_switch_prob", 0.5))), dtype=torch.float32)
+
+    def graph_batch(self, batch):
+        """Graph path: the host draw travels inside the batch as the ``mix`` tensor, so the step
+        engine stages it into the captured graph's static inputs and every replay mixes with
+        fresh values."""
+        if not self.mixing or len(batch) != 2:
+            return batch
+        x, y = batch
+        return x, y, self.draw_mix().to(x.device, non_blocking=True)
+
+    def soft_inputs(self, batch):
+        x, y = batch[0], batch[1]
+        if not (self.training and self.mixing):  # validation / test: hard labels, never mixed
+            return x, None, y, None, None
+        mix = batch[2] if len(batch) > 2 else self.draw_mix().to(x.device)  # eager path: drawn here
+        from . import ops
+
+        xm, yb, lam = ops.batch_mix(x, y, mix)
+        return xm, None, y, yb, lam
 
 
 class LitTextClassifier(LitClassifier):
@@ -169,6 +269,10 @@ class LitTextClassifier(LitClassifier):
     def forward(self, batch):
         y, x, x_mask = batch
         return self.model(x, x_mask), y
+
+    def soft_inputs(self, batch):
+        y, x, x_mask = batch
+        return x, x_mask, y, None, None
 
     def graph_batch(self, batch):
         return bucket_text_batch(batch, self.hparams.max_seq_len)
