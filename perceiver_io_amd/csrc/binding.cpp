@@ -127,6 +127,9 @@ unsigned check_errors_ce_head(bool);
 unsigned check_errors_topk_head(bool);
 unsigned check_errors_rowgemm(bool);
 unsigned check_errors_soft_ce_head(bool);
+unsigned check_errors_augment(bool);
+void batch_augment_launch(const uint8_t*, const float*, float*, int, int, int, int, int, int, const float*, const float*,
+                          hipStream_t);
 int soft_ce_row_tiles(int);
 void soft_ce_fwd_launch(int, const float*, const uint16_t*, const float*, const int64_t*, const int64_t*, const float*,
                         float, int, int, float*, int*, uint16_t*, float*, float*, float*, hipStream_t);
@@ -196,12 +199,13 @@ hipStream_t stream() { return at::hip::getCurrentHIPStream(); }
 #endif
 // checked builds: the device error words of every checked translation unit (bit 1: a token id
 // outside the embedding table, 2: a gather row outside its destination, 4: a class label
-// outside [0, V) ∪ {-100}); reset clears them
+// outside [0, V) ∪ {-100}, 8: a PE row index outside its table, 16: a batch_augment crop box that had to be
+// clamped into its source image); reset clears them
 int64_t check_errors(bool reset) {
   return (int64_t)(pio::check_errors_elementwise(reset) | pio::check_errors_mlm_head(reset) |
                    pio::check_errors_ce_head(reset) | pio::check_errors_topk_head(reset) |
                    pio::check_errors_rowgemm(reset) | pio::check_errors_pixel_head(reset) |
-                   pio::check_errors_soft_ce_head(reset));
+                   pio::check_errors_soft_ce_head(reset) | pio::check_errors_augment(reset));
 }
 bool checked_build() { return PIO_CHECKS != 0; }
 // checked builds, outside graph capture: wait for the kernel just launched and raise on any
@@ -215,7 +219,7 @@ void checked_sync(const char* what) {
   const int64_t e = check_errors(true);
   TORCH_CHECK(e == 0, "checked build: ", what, " saw out-of-range indices (error bits ", e,
               ": 1 token id >= vocab, 2 gather row out of range, 4 label outside [0, V) and != -100, 8 PE row index outside "
-              "the position-encoding table)");
+              "the position-encoding table, 16 batch_augment crop box outside its source image)");
 }
 
 // deterministic mode (trainer flag ``deterministic``): every reduction that would
@@ -1464,6 +1468,36 @@ std::vector<Tensor> batch_mix(Tensor x, Tensor y, Tensor mix) {
   return {out, yb, lam};
 }
 
+// crop box → bilinear resize → horizontal flip → normalize of a raw uint8 channels-last batch (csrc/augment.hip);
+// params (B, 8) fp32 on the device: {y0, x0, h, w, flip, 0, 0, 0} per sample, read by the kernel
+Tensor batch_augment(Tensor src, Tensor params, std::vector<double> mean, std::vector<double> std_, int64_t out_h,
+                     int64_t out_w) {
+  CHECK_CUDA(src); CHECK_CUDA(params);
+  CHECK_DT(src, torch::kUInt8); CHECK_DT(params, torch::kFloat32);
+  TORCH_CHECK(src.dim() == 4 && src.is_contiguous(), "batch_augment: src must be (B, Hs, Ws, C) uint8 contiguous");
+  const int64_t B = src.size(0), Hs = src.size(1), Ws = src.size(2), C = src.size(3);
+  TORCH_CHECK(B >= 1 && B < (1 << 16) && Hs >= 1 && Ws >= 1, "batch_augment: 1 <= B < 65536, a non-empty source");
+  TORCH_CHECK(C >= 1 && C <= 4, "batch_augment: 1 to 4 channels, got ", C);
+  TORCH_CHECK((int64_t)mean.size() == C && (int64_t)std_.size() == C, "batch_augment: mean / std need one value per channel");
+  TORCH_CHECK(params.dim() == 2 && params.size(0) == B && params.size(1) == 8 && params.is_contiguous() &&
+                  params.get_device() == src.get_device(),
+              "batch_augment: params must be (B, 8) fp32 contiguous on src's device");
+  TORCH_CHECK(out_h >= 1 && out_w >= 1, "batch_augment: out_hw must be positive");
+  const int64_t lim = (int64_t)1 << 30;
+  TORCH_CHECK(Hs * Ws * C < lim && out_h * out_w * C < lim && Hs < lim && Ws < lim && out_h < lim && out_w < lim,
+              "batch_augment: a sample (source or output) must hold fewer than 2^30 elements");
+  float mv[4], sv[4];
+  for (int64_t c = 0; c < C; ++c) {
+    mv[c] = (float)mean[c];
+    sv[c] = (float)std_[c];
+  }
+  Tensor out = torch::empty({B, out_h, out_w, C}, src.options().dtype(torch::kFloat32));
+  pio::batch_augment_launch(src.data_ptr<uint8_t>(), f32p(params), out.data_ptr<float>(), (int)B, (int)Hs, (int)Ws, (int)C,
+                            (int)out_h, (int)out_w, mv, sv, stream());
+  // no checked_sync: a clamped box has a defined result; the checked build's bit 16 waits for check_errors
+  return out;
+}
+
 Tensor embed_fwd(Tensor ids, Tensor E, Tensor P, double scale) {
   TORCH_CHECK(ids.is_contiguous() && E.is_contiguous() && P.is_contiguous());
   CHECK_DT(ids, torch::kInt64);
@@ -2257,6 +2291,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("bias"), py::arg("eps"), py::arg("lse"), py::arg("gout"), py::arg("count"), py::arg("dH"), py::arg("dW"),
         py::arg("db"), py::arg("accumulate"));
   m.def("batch_mix", &batch_mix, py::arg("x"), py::arg("y"), py::arg("mix"));
+  m.def("batch_augment", &batch_augment, py::arg("src"), py::arg("params"), py::arg("mean"), py::arg("std"),
+        py::arg("out_h"), py::arg("out_w"));
   m.def("embed_fwd", &embed_fwd);
   m.def("embed_bwd", &embed_bwd, py::arg("ids"), py::arg("g"), py::arg("dE"), py::arg("dP"), py::arg("scale"),
         py::arg("job_slab") = py::none(), py::arg("job_dsts") = std::vector<Tensor>(),

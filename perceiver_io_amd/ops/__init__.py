@@ -68,7 +68,9 @@ def check_device_errors(reset: bool = True) -> None:
       invalid tile ticket (bit 1).  The launch finishes either way (no GPU hang); this turns the
       corrupted forward into an error instead of silent training on garbage.
     * checked builds (``PERCEIVER_CHECKED=1``): the index-validation words — token ids, gather
-      rows and class labels outside their tables (the kernels clamped / skipped the access).
+      rows and class labels outside their tables (the kernels clamped / skipped the access), and
+      bit 16: a ``batch_augment`` crop box that reached outside its source image (clamped; the
+      call itself never raises for it).
       Outside a graph capture every checked launch raises at once (``checked_sync``); inside a
       replayed hipGraph nothing can.
 
@@ -91,7 +93,8 @@ def check_device_errors(reset: bool = True) -> None:
         if c:
             raise RuntimeError(f"checked build: out-of-range indices seen on the device (error bits {c:#x}: "
                                "1 token id >= vocab, 2 gather row out of range, 4 label outside [0, V) and != -100, "
-                               "8 PE row index outside the position-encoding table)")
+                               "8 PE row index outside the position-encoding table, "
+                               "16 batch_augment crop box outside its source image)")
 
 
 def use_hip(t: torch.Tensor) -> bool:
@@ -121,6 +124,38 @@ def batch_mix(x: torch.Tensor, y: torch.Tensor, mix: torch.Tensor):
     from . import emulation
 
     return emulation.batch_mix(x, y, mix)
+
+
+def _per_channel(v, C: int):
+    vals = [float(a) for a in (v if isinstance(v, (list, tuple)) else torch.as_tensor(v).reshape(-1).tolist())]
+    if len(vals) == 1:
+        vals = vals * C
+    if len(vals) != C:
+        raise ValueError(f"batch_augment: mean / std need 1 or {C} values, got {len(vals)}")
+    return vals
+
+
+def batch_augment(src: torch.Tensor, params: torch.Tensor, mean, std, out_hw) -> torch.Tensor:
+    """Crop → bilinear resize → horizontal flip → normalize of a raw ``uint8`` channels-last batch
+    ``src`` (B, Hs, Ws, C ≤ 4) → fp32 (B, out_h, out_w, C).  ``params`` (B, 8) fp32 holds per sample
+    ``{y0, x0, h, w, flip, 0, 0, 0}``: the crop box in source pixels (integers stored as floats)
+    and the flip flag (≥ 0.5: mirrored columns); ``mean`` / ``std``: one value per channel (or one
+    for all).  Same values as ``F.interpolate(box, out_hw, mode="bilinear", align_corners=False)``
+    → flip → ``(v / 255 − mean) / std``; a box of the output size is copied without any
+    interpolation arithmetic, bit for bit the host pipeline's result.  The box is clamped into
+    the source in every build.  HIP path: one kernel that reads ``params`` from device memory
+    (``csrc/augment.hip``) — no host sync, and a replayed hipGraph augments with whatever words
+    were staged for that step."""
+    if src.dtype != torch.uint8 or src.dim() != 4:
+        raise ValueError(f"batch_augment: src must be a (B, Hs, Ws, C) uint8 batch, got {tuple(src.shape)} {src.dtype}")
+    C = src.shape[3]
+    mean, std = _per_channel(mean, C), _per_channel(std, C)
+    if use_hip(src):
+        p = params.to(device=src.device, dtype=torch.float32).contiguous()
+        return ext.require().batch_augment(src.contiguous(), p, mean, std, int(out_hw[0]), int(out_hw[1]))
+    from . import emulation
+
+    return emulation.batch_augment(src, params, mean, std, out_hw)
 
 
 from . import attention, fused, masking, mlm_head, optim  # noqa: E402,F401

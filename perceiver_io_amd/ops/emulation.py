@@ -683,6 +683,68 @@ def batch_mix(x, y, mix):
     return out, y.flip(0).contiguous(), lam.expand(B).contiguous()
 
 
+def _augment_word(v, lo, hi):
+    """A crop-box word as an integer in [lo, hi] (``hi`` an int or a per-sample tensor): NaN and
+    anything below ``lo`` → ``lo``, anything above ``hi`` → ``hi``, fractions truncated."""
+    hi = torch.as_tensor(hi, device=v.device)
+    v = torch.nan_to_num(v.float(), nan=float(lo), posinf=float(1 << 30), neginf=float(lo))
+    return torch.minimum(v.clamp(min=float(lo)).trunc().long(), hi.long())
+
+
+def augment_boxes(params, Hs: int, Ws: int):
+    """``params`` (B, 8) → the clamped integer boxes ``(y0, x0, h, w)`` and the flip flags, each (B,)."""
+    p = params.detach().float()
+    y0 = _augment_word(p[:, 0], 0, Hs - 1)
+    x0 = _augment_word(p[:, 1], 0, Ws - 1)
+    h = _augment_word(p[:, 2], 1, Hs - y0)
+    w = _augment_word(p[:, 3], 1, Ws - x0)
+    return y0, x0, h, w, p[:, 4] >= 0.5
+
+
+def _augment_axis(n_out: int, size, dev, flip=None):
+    """Bilinear source coordinates of one axis (``align_corners=False``): output index k of
+    ``n_out``, box extent ``size`` (B,) → (k0, k1, λ), each (B, n_out), inside the box."""
+    k = torch.arange(n_out, device=dev)[None, :].expand(size.shape[0], n_out)
+    if flip is not None:
+        k = torch.where(flip[:, None], n_out - 1 - k, k)
+    scale = size.float() / torch.full_like(size, n_out).float()
+    s = ((k.float() + 0.5) * scale[:, None] - 0.5).clamp(min=0.0)
+    k0 = torch.minimum(s.floor().long(), size[:, None] - 1)
+    k1 = torch.minimum(k0 + 1, size[:, None] - 1)
+    return k0, k1, s - k0.float()
+
+
+def batch_augment(src, params, mean, std, out_hw):
+    """Crop box → bilinear resize → horizontal flip → normalize of a raw uint8 channels-last batch
+    ``src`` (B, Hs, Ws, C) → fp32 (B, oh, ow, C), the formulas of ``csrc/augment.hip`` in fp32 with
+    each operation rounded on its own.  ``params`` (B, 8): ``{y0, x0, h, w, flip, 0, 0, 0}`` per
+    sample, the box clamped into the source (NaN / negative offsets → 0, NaN / zero / negative
+    sizes → 1).  Output (i, j) (j mirrored when flipped) reads ``sy = max((i + 0.5)·h/oh − 0.5, 0)``,
+    rows ``⌊sy⌋`` and ``min(⌊sy⌋ + 1, h − 1)`` with weight ``λ = sy − ⌊sy⌋``, columns alike; the raw
+    0..255 values are interpolated, then ``(v / 255 − mean) / std`` (true divisions: by tensors, a
+    Python-scalar divisor becomes a multiplication by the reciprocal on the GPU).  A box of the
+    output size is a plain copy (λ = 0 everywhere)."""
+    B, Hs, Ws, C = src.shape
+    oh, ow = int(out_hw[0]), int(out_hw[1])
+    dev = src.device
+    y0, x0, h, w, flip = augment_boxes(params.to(dev), Hs, Ws)
+    i0, i1, ly = _augment_axis(oh, h, dev)
+    j0, j1, lx = _augment_axis(ow, w, dev, flip)
+    s = src.float()
+    bb = torch.arange(B, device=dev)[:, None, None]
+    r0, r1 = (y0[:, None] + i0)[:, :, None], (y0[:, None] + i1)[:, :, None]
+    c0, c1 = (x0[:, None] + j0)[:, None, :], (x0[:, None] + j1)[:, None, :]
+    v00, v01, v10, v11 = s[bb, r0, c0], s[bb, r0, c1], s[bb, r1, c0], s[bb, r1, c1]  # (B, oh, ow, C)
+    lx, ly = lx[:, None, :, None], ly[:, :, None, None]
+    mx, my = 1.0 - lx, 1.0 - ly
+    v = my * (mx * v00 + lx * v01) + ly * (mx * v10 + lx * v11)
+    copy = (h == oh) & (w == ow)
+    v = torch.where(copy[:, None, None, None], v00, v)
+    m = torch.as_tensor(mean, dtype=torch.float32, device=dev).reshape(-1).expand(C)
+    sd = torch.as_tensor(std, dtype=torch.float32, device=dev).reshape(-1).expand(C)
+    return ((v / torch.full((1,), 255.0, device=dev) - m) / sd).contiguous()
+
+
 def embed_fwd(ids, E, P, scale):
     return E[ids] * scale + P[: ids.shape[1]].unsqueeze(0)
 

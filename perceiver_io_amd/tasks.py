@@ -180,6 +180,8 @@ class LitImageClassifier(LitClassifier):
         super().__init__(*args, **kwargs)
         self.model = self.create_model()
         self._mix_rng = None
+        self._aug_rng = None
+        self.augment = None  # a DeviceAugment set directly (tests); else the data module's
 
     def create_model(self):
         hp = self.hparams
@@ -195,8 +197,58 @@ class LitImageClassifier(LitClassifier):
         return PerceiverIO(encoder, decoder)
 
     def forward(self, batch):
-        x, y = batch[0], batch[1]
+        x, y, _ = self.inputs(batch)
         return self.model(x), y
+
+    # -- device-side augmentation ---------------------------------------------------------------
+    # batch layouts: (x, y), (x, y, mix) and (x, y, mix | None, aug); ``aug`` is the (B, 8) block of
+    # DeviceAugment.draw for a raw uint8 ``x``
+    def _host_rng(self, tag: int):
+        import numpy as np
+
+        tr = self._trainer
+        seed = getattr(tr, "seed", None) if tr is not None else None
+        rank = getattr(getattr(tr, "dist", None), "rank", 0) if tr is not None else 0
+        base = int(seed) if seed is not None else int(torch.initial_seed() % (1 << 31))
+        return np.random.default_rng([base, int(rank), tag])
+
+    @property
+    def augmenter(self):
+        """The ``DeviceAugment`` of this module: its own ``augment`` attribute, else the trainer's
+        data module's."""
+        if self.augment is not None:
+            return self.augment
+        tr = self._trainer
+        return getattr(getattr(tr, "datamodule", None), "augment", None) if tr is not None else None
+
+    def draw_augment(self, B: int, train: bool) -> torch.Tensor:
+        """This micro-batch's augmentation words as a host tensor, drawn from the module's own
+        ``numpy.random.Generator`` (seeded from the trainer seed and rank on first use); the data
+        loader's workers draw nothing on this path."""
+        if self._aug_rng is None:
+            self._aug_rng = self._host_rng(0x415547)
+        return torch.from_numpy(self._require_augmenter().draw(self._aug_rng, int(B), train))
+
+    def _require_augmenter(self):
+        aug = self.augmenter
+        if aug is None:
+            raise RuntimeError("the batch holds raw uint8 images but there is no augmenter: use a data module with "
+                               "device_augment=true (its `augment`), or set the module's `augment` attribute")
+        return aug
+
+    def inputs(self, batch):
+        """→ (x fp32, y, mix words or None) of a batch: a raw uint8 ``x`` goes through
+        ``ops.batch_augment`` first, with the words the batch carries (graph path) or a draw made
+        here (eager path; the evaluation draw outside training)."""
+        x, y = batch[0], batch[1]
+        mix = batch[2] if len(batch) > 2 else None
+        if x.dtype == torch.uint8:
+            augmenter = self._require_augmenter()
+            aug = batch[3] if len(batch) > 3 else None
+            if aug is None:
+                aug = self.draw_augment(x.shape[0], self.training)
+            x = augmenter.apply(x, aug)
+        return x, y, mix
 
     # -- MixUp / CutMix ------------------------------------------------------------------------
     @property
@@ -212,32 +264,30 @@ class LitImageClassifier(LitClassifier):
         """This micro-batch's mix words as a host tensor: one draw from the module's own
         ``numpy.random.Generator``, seeded from the trainer seed (rank-shifted) on first use."""
         if self._mix_rng is None:
-            import numpy as np
-
-            tr = self._trainer
-            seed = getattr(tr, "seed", None) if tr is not None else None
-            rank = getattr(getattr(tr, "dist", None), "rank", 0) if tr is not None else 0
-            base = int(seed) if seed is not None else int(torch.initial_seed() % (1 << 31))
-            self._mix_rng = np.random.default_rng([base, int(rank), 0x4D4958])
+            self._mix_rng = self._host_rng(0x4D4958)
         hp = self.hparams
         return torch.tensor(draw_mix(self._mix_rng, tuple(hp.image_shape)[:2], float(hp.get("mixup_alpha", 0.0)),
                                      float(hp.get("cutmix_alpha", 0.0)), float(hp.get("mix_prob", 1.0)),
                                      float(hp.get("mix_switch_prob", 0.5))), dtype=torch.float32)
 
     def graph_batch(self, batch):
-        """Graph path: the host draw travels inside the batch as the ``mix`` tensor, so the step
-        engine stages it into the captured graph's static inputs and every replay mixes with
-        fresh values."""
-        if not self.mixing or len(batch) != 2:
+        """Graph path: the host draws travel inside the batch — ``(x, y, mix)`` when mixing,
+        ``(x, y, mix | None, aug)`` for a raw uint8 ``x`` — so the step engine stages them into the
+        captured graph's static inputs and every replay mixes / augments with fresh values."""
+        if len(batch) != 2:
             return batch
         x, y = batch
-        return x, y, self.draw_mix().to(x.device, non_blocking=True)
+        mix = self.draw_mix().to(x.device, non_blocking=True) if self.mixing else None
+        if x.dtype == torch.uint8:
+            return x, y, mix, self.draw_augment(x.shape[0], True).to(x.device, non_blocking=True)
+        return batch if mix is None else (x, y, mix)
 
     def soft_inputs(self, batch):
-        x, y = batch[0], batch[1]
+        x, y, mix = self.inputs(batch)
         if not (self.training and self.mixing):  # validation / test: hard labels, never mixed
             return x, None, y, None, None
-        mix = batch[2] if len(batch) > 2 else self.draw_mix().to(x.device)  # eager path: drawn here
+        if mix is None:
+            mix = self.draw_mix().to(x.device)  # eager path: drawn here
         from . import ops
 
         xm, yb, lam = ops.batch_mix(x, y, mix)
