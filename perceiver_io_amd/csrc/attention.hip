@@ -33,20 +33,6 @@ namespace pio {
 
 constexpr int KT = 64;  // keys per forward tile
 
-struct AttnArgs {
-  const uint16_t* q; long long q_bs; int q_rs;
-  const uint16_t* k; long long k_bs; int k_rs;
-  const uint16_t* v; long long v_bs; int v_rs;
-  const uint8_t* kmask;  // (B, Nk), nonzero = padding key; may be null
-  int B, H, Nq, Nk;
-  float scale_log2;      // softmax scale * log2(e)
-  float scale;           // softmax scale (backward)
-  uint32_t drop_thresh;  // dropout probability * 2^32 (0 = off)
-  float drop_scale;      // 1 / (1 - p)
-  const int64_t* seedp;  // device seed of the call (common.h DropCfg); read only when drop_thresh
-  uint32_t site;
-};
-
 // ------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------
@@ -764,17 +750,6 @@ __global__ __launch_bounds__(64 * NW, (QR == 2 && !DRP) ? 4 : 1) void attn_bwd_k
   PIO_WG_END();
 }
 
-// host ABI check (binding.cpp mirrors these structs)
-int abi_struct_size(int which) {
-  switch (which) {
-    case 0: return (int)sizeof(DropCfg);
-    case 1: return (int)sizeof(PostAttnGrads);
-    case 2: return (int)sizeof(SlabJob);
-    case 3: return (int)sizeof(AttnArgs);
-    default: return -1;
-  }
-}
-
 // zero rows of a strided fp32 (B, N, W) view (dQ accumulator when several key blocks add into it)
 __global__ void zero_rows_kernel(float* __restrict__ p, long long bs, int rs, int N, int W, long long total) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
@@ -931,59 +906,49 @@ int attn_bwd_zero_plan(int B, int H, int Nq, int Nk, int D) {
 }
 
 template <int D, int NW>
-static void bwd_launch_t(const AttnArgs& a, const uint16_t* dO, const float* LSE, float* delta, float* dq,
-                         long long dq_bs, int dq_rs, float* dk, long long dk_bs, int dk_rs, float* dv, long long dv_bs,
-                         int dv_rs, int kv_acc, long long dq_kbs, int qsplit_ok, int dq_zeroed, hipStream_t st) {
+static void bwd_launch_t(const AttnBwdArgs& b, hipStream_t st) {
+  const AttnArgs& a = b.a;
+  const Rows3 &dq = b.dq, &dk = b.dk, &dv = b.dv;
+  const int kv_acc = b.kv_acc;
   const int nkb = (a.Nk + 32 * NW - 1) / (32 * NW);
   const int nqt = (a.Nq + 31) / 32;
-  const int nqs = bwd_query_splits(nkb, a.H, a.B, a.Nq, qsplit_ok);
+  const int nqs = bwd_query_splits(nkb, a.H, a.B, a.Nq, b.qsplit_ok);
   const int tps = (nqt + nqs - 1) / nqs;
-  if (nqs > 1 && !kv_acc && !(dq_zeroed & 2)) {  // the splits add into dK / dV (bit 1: cleared by the caller)
+  if (nqs > 1 && !kv_acc && !(b.dq_zeroed & 2)) {  // the splits add into dK / dV (bit 1: cleared by the caller)
     const long long total = (long long)a.B * a.Nk * a.H * D;
     const unsigned zb = (unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipLaunchKernelGGL(zero_rows_kernel, dim3(zb), dim3(256), 0, st, dk, dk_bs, dk_rs, a.Nk, a.H * D, total);
-    hipLaunchKernelGGL(zero_rows_kernel, dim3(zb), dim3(256), 0, st, dv, dv_bs, dv_rs, a.Nk, a.H * D, total);
+    hipLaunchKernelGGL(zero_rows_kernel, dim3(zb), dim3(256), 0, st, dk.p, dk.bs, dk.rs, a.Nk, a.H * D, total);
+    hipLaunchKernelGGL(zero_rows_kernel, dim3(zb), dim3(256), 0, st, dv.p, dv.bs, dv.rs, a.Nk, a.H * D, total);
   }
   // several key blocks add into dQ (fp32 atomics), unless each stores its own partial slice
   // (deterministic mode: dq_kbs > 0, summed by the caller)
-  const int atomic = nkb > 1 && dq_kbs == 0;
-  if (atomic && !(dq_zeroed & 1)) {
+  const int atomic = nkb > 1 && b.dq_kbs == 0;
+  if (atomic && !(b.dq_zeroed & 1)) {
     const long long total = (long long)a.B * a.Nq * a.H * D;
     hipLaunchKernelGGL(zero_rows_kernel, dim3((unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096)), dim3(256), 0,
-                       st, dq, dq_bs, dq_rs, a.Nq, a.H * D, total);
+                       st, dq.p, dq.bs, dq.rs, a.Nq, a.H * D, total);
   }
   dim3 grid(nkb * nqs, a.H, a.B);
-  constexpr bool small_lds = true;
+#define BWDL(...)                                                                                                  \
+  hipLaunchKernelGGL((attn_bwd_kernel<D, NW, ##__VA_ARGS__>), grid, dim3(64 * NW), 0, st, a, b.dO, b.LSE, b.delta, dq.p, \
+                     dq.bs, dq.rs, dk.p, dk.bs, dk.rs, dv.p, dv.bs, dv.rs, atomic, kv_acc, b.dq_kbs, nqs, tps, SlabJob{})
   // head width 16, no dropout, a grid wider than the chip: the two-query-tile variant at ≤ 128
   // VGPRs runs two 8-wave workgroups per CU (1.342 → 1.327 ms on the headline step, r5)
   const bool wide = D == 16 && NW == 8 && !a.drop_thresh && a.Nq > 64 &&
                     (long long)grid.x * grid.y * grid.z > 256;
   if (wide) {
-    if (a.kmask == nullptr && a.Nk % (32 * NW) == 0)
-      hipLaunchKernelGGL((attn_bwd_kernel<D, NW, 2, false, false, false>), grid, dim3(64 * NW), 0, st, a, dO, LSE, delta,
-                         dq, dq_bs, dq_rs, dk, dk_bs, dk_rs, dv, dv_bs, dv_rs, atomic, kv_acc, dq_kbs, nqs, tps, SlabJob{});
-    else
-      hipLaunchKernelGGL((attn_bwd_kernel<D, NW, 2, false, true, false>), grid, dim3(64 * NW), 0, st, a, dO, LSE, delta,
-                         dq, dq_bs, dq_rs, dk, dk_bs, dk_rs, dv, dv_bs, dv_rs, atomic, kv_acc, dq_kbs, nqs, tps, SlabJob{});
+    if (a.kmask == nullptr && a.Nk % (32 * NW) == 0) BWDL(2, false, false, false);
+    else BWDL(2, false, true, false);
     return;
   }
   // ≤ 64 queries (few-query cross-attention): the small-LDS variants let several workgroups
   // share a CU
-  if (a.Nq <= 32 && small_lds)
-    hipLaunchKernelGGL((attn_bwd_kernel<D, NW, 1>), grid, dim3(64 * NW), 0, st, a, dO, LSE, delta, dq, dq_bs, dq_rs,
-                       dk, dk_bs, dk_rs, dv, dv_bs, dv_rs, atomic, kv_acc, dq_kbs, nqs, tps, SlabJob{});
-  else if (a.Nq <= 64 && small_lds)
-    hipLaunchKernelGGL((attn_bwd_kernel<D, NW, 2>), grid, dim3(64 * NW), 0, st, a, dO, LSE, delta, dq, dq_bs, dq_rs,
-                       dk, dk_bs, dk_rs, dv, dv_bs, dv_rs, atomic, kv_acc, dq_kbs, nqs, tps, SlabJob{});
-  else if (a.kmask == nullptr && a.Nk % (32 * NW) == 0)
-    hipLaunchKernelGGL((attn_bwd_kernel<D, NW, 0, false, false>), grid, dim3(64 * NW), 0, st, a, dO, LSE, delta, dq,
-                       dq_bs, dq_rs, dk, dk_bs, dk_rs, dv, dv_bs, dv_rs, atomic, kv_acc, dq_kbs, nqs, tps, SlabJob{});
-  else
-    hipLaunchKernelGGL((attn_bwd_kernel<D, NW>), grid, dim3(64 * NW), 0, st, a, dO, LSE, delta, dq, dq_bs, dq_rs, dk,
-                       dk_bs, dk_rs, dv, dv_bs, dv_rs, atomic, kv_acc, dq_kbs, nqs, tps, SlabJob{});
+  if (a.Nq <= 32) BWDL(1);
+  else if (a.Nq <= 64) BWDL(2);
+  else if (a.kmask == nullptr && a.Nk % (32 * NW) == 0) BWDL(0, false, false);
+  else BWDL();
+#undef BWDL
 }
-
-void slab_reduce_launch(const SlabJob& job, hipStream_t st);  // elementwise.hip
 
 // key blocks of the backward grid (dQ partial slices in deterministic mode)
 int attn_bwd_key_blocks(int Nk, int D) {
@@ -991,33 +956,31 @@ int attn_bwd_key_blocks(int Nk, int D) {
   return (Nk + 32 * nw - 1) / (32 * nw);
 }
 
-void attn_bwd_launch(const AttnArgs& a, int D, const uint16_t* O, const uint16_t* dO, const float* LSE, float* delta,
-                     float* dq, long long dq_bs, int dq_rs, float* dk, long long dk_bs, int dk_rs, float* dv,
-                     long long dv_bs, int dv_rs, bool compute_delta, bool kv_acc, long long dq_kbs, int qsplit_ok,
-                     int dq_zeroed, hipStream_t st) {
+void attn_bwd_launch(const AttnBwdArgs& b, int D, hipStream_t st) {
+  const AttnArgs& a = b.a;
   // delta = rowsum(dO∘O) is normally produced by the post-attention backward kernel;
   // compute it here otherwise.  dQ needs no zero fill from the caller.
   const int rows = a.B * a.Nq;
-  if (compute_delta)
-    hipLaunchKernelGGL(attn_bwd_prep_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, dO, O, delta, (float*)nullptr,
-                       rows, a.H, D, dq_rs);
+  if (b.compute_delta)
+    hipLaunchKernelGGL(attn_bwd_prep_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, b.dO, b.O, b.delta, (float*)nullptr,
+                       rows, a.H, D, b.dq.rs);
   if (decode_bwd_ok(a, D)) {  // one query: its dK / dV rows are its own (no sum over queries)
     const dim3 grid((unsigned)a.B, (unsigned)a.H);
-    hipLaunchKernelGGL((attn_decode_bwd_kernel<128>), grid, dim3(64), 0, st, a, dO, LSE, delta, dq, dq_bs, dq_rs, dk,
-                       dk_bs, dk_rs, dv, dv_bs, dv_rs, (int)kv_acc);
+    hipLaunchKernelGGL((attn_decode_bwd_kernel<128>), grid, dim3(64), 0, st, a, b.dO, b.LSE, b.delta, b.dq.p, b.dq.bs,
+                       b.dq.rs, b.dk.p, b.dk.bs, b.dk.rs, b.dv.p, b.dv.bs, b.dv.rs, (int)b.kv_acc);
     return;
   }
   switch (D) {  // waves per workgroup: 8 for d ≤ 32, 4 above (keys per block = 32 × waves)
     case 16:  // ≤ 64 keys (the 64-latent self-attention of the text classifiers / MLM-64): 2 waves, not 6 idle of 8
-      if (a.Nk <= 64) bwd_launch_t<16, 2>(a, dO, LSE, delta, dq, dq_bs, dq_rs, dk, dk_bs, dk_rs, dv, dv_bs, dv_rs, kv_acc, dq_kbs, qsplit_ok, dq_zeroed, st);
-      else bwd_launch_t<16, 8>(a, dO, LSE, delta, dq, dq_bs, dq_rs, dk, dk_bs, dk_rs, dv, dv_bs, dv_rs, kv_acc, dq_kbs, qsplit_ok, dq_zeroed, st);
+      if (a.Nk <= 64) bwd_launch_t<16, 2>(b, st);
+      else bwd_launch_t<16, 8>(b, st);
       break;
     case 32:  // ≤ 64 keys (the image configs' 32-latent self-attention): 2 waves, not 6 idle of 8
-      if (a.Nk <= 64) bwd_launch_t<32, 2>(a, dO, LSE, delta, dq, dq_bs, dq_rs, dk, dk_bs, dk_rs, dv, dv_bs, dv_rs, kv_acc, dq_kbs, qsplit_ok, dq_zeroed, st);
-      else bwd_launch_t<32, 8>(a, dO, LSE, delta, dq, dq_bs, dq_rs, dk, dk_bs, dk_rs, dv, dv_bs, dv_rs, kv_acc, dq_kbs, qsplit_ok, dq_zeroed, st);
+      if (a.Nk <= 64) bwd_launch_t<32, 2>(b, st);
+      else bwd_launch_t<32, 8>(b, st);
       break;
-    case 64: bwd_launch_t<64, 4>(a, dO, LSE, delta, dq, dq_bs, dq_rs, dk, dk_bs, dk_rs, dv, dv_bs, dv_rs, kv_acc, dq_kbs, qsplit_ok, dq_zeroed, st); break;
-    case 128: bwd_launch_t<128, 4>(a, dO, LSE, delta, dq, dq_bs, dq_rs, dk, dk_bs, dk_rs, dv, dv_bs, dv_rs, kv_acc, dq_kbs, qsplit_ok, dq_zeroed, st); break;
+    case 64: bwd_launch_t<64, 4>(b, st); break;
+    case 128: bwd_launch_t<128, 4>(b, st); break;
     default: break;
   }
 }

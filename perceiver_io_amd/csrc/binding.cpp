@@ -5,188 +5,10 @@
 #include <ATen/hip/HIPContext.h>
 #include <hip/hip_runtime.h>
 
-#include "pe_args.h"
+#include "host_api.h"
 
 #include <unordered_map>
 #include <vector>
-
-namespace pio {
-struct AttnArgs {
-  const uint16_t* q; long long q_bs; int q_rs;
-  const uint16_t* k; long long k_bs; int k_rs;
-  const uint16_t* v; long long v_bs; int v_rs;
-  const uint8_t* kmask;
-  int B, H, Nq, Nk;
-  float scale_log2, scale;
-  uint32_t drop_thresh;
-  float drop_scale;
-  const int64_t* seedp;
-  uint32_t site;
-};
-struct DropCfg {  // common.h
-  const int64_t* seed;
-  uint32_t site;
-  uint32_t thresh;
-  float scale;
-};
-struct PostAttnGrads { float *dWo, *dbo, *dg2, *dbe2, *dW1, *db1, *dW2, *db2; int vrs; int slab; };
-constexpr int kMaxSlabSegs = 16, kSlabColsPerBlock = 1024;  // common.h
-struct SlabJob {
-  const float* slab;
-  int S, P, nbx, nblk;
-  int det;
-  int n;
-  float* dst[kMaxSlabSegs];
-  int off[kMaxSlabSegs];
-  int len[kMaxSlabSegs];
-  float* zero_p;  // (mirror of csrc/common.h)
-  long long zero_n4;
-};
-}  // namespace pio
-#include "persist_args.h"
-#include "sb_args.h"
-namespace pio {
-bool sb_fwd_launch(const SBFwdArgs&, int C, hipStream_t);
-bool sb_bwd_launch(const SBBwdArgs&, int C, hipStream_t);
-bool sb_wgrad_launch(SBWgradArgs, int C, const SlabJob&, hipStream_t);
-bool sa_block_fwd_launch(const SABlockFwdArgs&, hipStream_t);
-unsigned persist_errors(bool);
-void persist_set_spin_limit(unsigned);
-int persist_sync_words(int);
-
-// sizes of the structs above as the kernel translation units see them (checked at import: a
-// mirror that drifts from common.h / attention.hip would hand the kernels garbage pointers)
-int abi_struct_size(int which);
-void attn_fwd_launch(const AttnArgs&, int, uint16_t*, float*, float*, float*, int, hipStream_t);
-void attn_bwd_launch(const AttnArgs&, int, const uint16_t*, const uint16_t*, const float*, float*, float*, long long,
-                     int, float*, long long, int, float*, long long, int, bool, bool, long long, int, int, hipStream_t);
-int attn_bwd_key_blocks(int, int);
-bool attn_bwd_bf16_ok(const AttnArgs&, int);
-bool attn_bwd_bf16_launch(const AttnArgs&, int, const uint16_t*, const float*, const float*, uint16_t*, long long, int,
-                          uint16_t*, long long, int, uint16_t*, long long, int, const SlabJob&, hipStream_t);
-int attn_bwd_zero_plan(int, int, int, int, int);
-void ln_linear_fwd_launch(const void*, bool, int, int, int, const float*, const float*, float, const uint16_t*, int,
-                          const float*, int, int, const float*, int, void*, bool, int, float*, float*, const float*, int,
-                          int, int, const long long*, hipStream_t);
-void post_attn_fwd_launch(int, const uint16_t*, const float*, const uint16_t*, const float*, const float*,
-                          const float*, float, const uint16_t*, const float*, const uint16_t*, const float*, float*,
-                          float*, float*, float*, uint16_t*, int, int, const DropCfg&, hipStream_t);
-void post_attn_ln_linear_fwd_launch(int, const uint16_t*, const float*, const uint16_t*, const float*, const float*,
-                                    const float*, float, const uint16_t*, const float*, const uint16_t*, const float*,
-                                    float*, float*, float*, float*, uint16_t*, int, int, const float*, const float*,
-                                    const uint16_t*, const float*, uint16_t*, float*, float*, const DropCfg&,
-                                    hipStream_t);
-bool sa_layer_fwd_launch(const uint16_t*, int, float, uint16_t*, float*, const float*, const uint16_t*, const float*,
-                         const float*, const float*, float, const uint16_t*, const float*, const uint16_t*, const float*,
-                         float*, float*, float*, float*, uint16_t*, int, const float*, const float*, const uint16_t*,
-                         const float*, uint16_t*, float*, float*, const DropCfg&, int, hipStream_t);
-bool ln_linear_post_attn_bwd_launch(int, const void*, bool, const uint16_t*, const float*, const float*, const float*,
-                                    const float*, const float*, const float*, float*, float*, float*, float*,
-                                    const float*, const float*, const float*, const uint16_t*, const uint16_t*,
-                                    const uint16_t*, const uint16_t*, const uint16_t*, const float*, const float*,
-                                    float*, uint16_t*, float*, int, const PostAttnGrads&, int, const SlabJob&,
-                                    const DropCfg&, int, const uint16_t*, const float*, uint16_t*, float, hipStream_t);
-void post_attn_bwd_launch(int, const float*, const float*, const float*, const float*, const uint16_t*,
-                          const uint16_t*, const uint16_t*, const uint16_t*, const uint16_t*, const float*,
-                          const float*, float*, uint16_t*, float*, int, const PostAttnGrads&, int, const SlabJob&,
-                          const DropCfg&, hipStream_t);
-void ln_linear_bwd_launch(const void*, bool, int, int, const uint16_t*, int, int, const void*, bool, int, const float*,
-                          const float*, const float*, const float*, const float*, int, float*, int, float*, float*,
-                          float*, float*, int, int, int, int, const float*, int, int, int, const long long*, const SlabJob&,
-                          hipStream_t);
-void wgrad_launch(const void*, bool, int, int, const void*, bool, int, int, int, const float*, const float*,
-                  const float*, const float*, int, int, float*, float*, int, int, const float*, int, int, int,
-                  const long long*, hipStream_t);
-void ce_fwd_launch(int, const float*, const int64_t*, const int64_t*, const uint16_t*, const float*, int, int, float*,
-                   float*, float*, float*, float*, float*, unsigned*, uint16_t*, int, float*, long long, int, hipStream_t);
-int ce_combine_blocks(int);
-int ce2_num_splits(int, int);
-int ce2_bwd_splits(int, int);
-int ce2_row_blocks(int);
-void ce2_fwd_launch(const float*, const int64_t*, const int64_t*, const uint16_t*, const float*, int, int, int, float2*,
-                    float*, float*, uint16_t*, float*, float*, int, float*, float*, unsigned*, unsigned*, float*,
-                    long long, hipStream_t);
-void ce2_bwd_launch(const uint16_t*, const int64_t*, const uint16_t*, const float*, const float*, const float*,
-                    const float2*, int, const float*, const float*, int, int, float*, float*, float*, int, float*, long long,
-                    const int64_t*, hipStream_t);
-int ce_num_splits(int, int);
-int ce_dw_splits(int, int);
-int vocab_topk_splits(int, int);
-int vocab_topk_kt(int);
-void vocab_topk_launch(int, const float*, const int64_t*, long long, const uint16_t*, const float*, int, int, int, int,
-                       float*, int*, float2*, float*, int64_t*, float*, hipStream_t);
-void mlm_select_launch(const int64_t*, int, int, int, int, int64_t*, int64_t*, int*, int64_t*, int64_t*, float*, bool*, bool*,
-                       const float*, int, float*, hipStream_t);
-void ce_bwd_launch(int, const uint16_t*, const int64_t*, const uint16_t*, const float*, const float*, const float*,
-                   const float*, int, int, float*, long long, const int64_t*, float*, float*, int, float*, int, hipStream_t);
-void embed_fwd_launch(const int64_t*, const float*, const float*, float*, long long, int, int, float, long long,
-                      hipStream_t);
-unsigned check_errors_elementwise(bool);
-unsigned check_errors_mlm_head(bool);
-unsigned check_errors_ce_head(bool);
-unsigned check_errors_topk_head(bool);
-unsigned check_errors_rowgemm(bool);
-unsigned check_errors_soft_ce_head(bool);
-unsigned check_errors_augment(bool);
-void batch_augment_launch(const uint8_t*, const float*, float*, int, int, int, int, int, int, const float*, const float*,
-                          hipStream_t);
-int soft_ce_row_tiles(int);
-void soft_ce_fwd_launch(int, const float*, const uint16_t*, const float*, const int64_t*, const int64_t*, const float*,
-                        float, int, int, float*, int*, uint16_t*, float*, float*, float*, hipStream_t);
-void soft_ce_bwd_launch(int, const uint16_t*, const uint16_t*, const float*, const int64_t*, const int64_t*,
-                        const float*, float, const float*, const float*, const float*, int, int, float*, float*, float*,
-                        int, hipStream_t);
-void batch_mix_launch(const float*, const int64_t*, const float*, float*, int64_t*, float*, int, int, int, int,
-                      hipStream_t);
-void embed_bwd_launch(const int64_t*, const float*, float*, float*, int, int, int, float, hipStream_t);
-void embed_bwd_sorted_launch(const int64_t*, const int64_t*, const float*, float*, long long, int, float, hipStream_t);
-bool embed_bwd_local_launch(const int64_t*, const float*, float*, float*, int, int, int, float, const SlabJob&,
-                            hipStream_t);
-void text_mask_launch(const int64_t*, const bool*, int64_t*, int64_t*, int64_t*, long long, int, int, float, int,
-                      uint32_t, int, hipStream_t);
-int stage_step_launch(void* const*, const void* const*, const long long*, int, float*, const float*, int, long long*,
-                      const long long*, int, hipStream_t);
-void sumsq_launch(const float*, long long, float*, hipStream_t);
-void index_add_rows_launch(float*, long long, const int64_t*, const float*, long long, int, hipStream_t);
-void gather_rows_launch(float*, const float*, long long, const int64_t*, long long, int, hipStream_t);
-void batch_sum2_launch(const float*, const float*, float*, float*, int, long long, long long, int, hipStream_t);
-void pe_gemm_launch(const uint16_t*, const uint16_t*, void*, bool, int, int, int, int, hipStream_t);
-struct PeGradTargets { float *dWa, *dWb, *db, *dg, *dbeta; };
-int pe_grad_splits(int);
-void pe_grads_launch(const uint16_t*, const float*, int, int, int, const float*, int, float*, float*, float*,
-                     const float*, const float*, const float*, const float*, int, int, int, PeGradTargets, hipStream_t);
-void pe_weight_prep_launch(const float*, const float*, int, const float*, const float*, const float*, int, int, int, int,
-                           uint16_t*, float*, float*, float*, float*, hipStream_t);
-int pixel_ce_blocks(long long);
-void pixel_ce_fwd_launch(int, int, const float*, const float*, const float*, const int64_t*, const float*, long long,
-                         float*, float*, float*, hipStream_t);
-void pixel_ce_bwd_launch(int, int, const float*, const float*, const float*, const int64_t*, const float*,
-                         const float*, const float*, long long, float*, float*, float*, float*, hipStream_t);
-void pixel_predict_launch(int, int, const float*, const float*, const float*, const int64_t*, const bool*, const int64_t*,
-                          long long, long long, long long, uint8_t*, float*, uint8_t*, int*, hipStream_t);
-void nonzero_compact_launch(const float*, int, long long, long long, int, int, int*, float*, int64_t*, bool*, int*,
-                            hipStream_t);
-unsigned check_errors_pixel_head(bool);
-void adamw_launch(float*, float*, float*, float*, uint16_t*, long long, const float*, float, float, float, float,
-                  int, int, const float*, float*, int, const float*, hipStream_t);
-int lamb_chunk_elems();
-void lamb_launch(float*, float*, float*, float*, uint16_t*, long long, const float*, const long long*, long long,
-                 const int*, const float*, int, float*, float*, float, float, float, int, const float*, float*, int,
-                 const float*, hipStream_t);
-void cast_bf16_launch(const float*, uint16_t*, long long, hipStream_t);
-void reduce_probe_launch(const float*, float*, hipStream_t);
-void fold_replicas_launch(float*, float*, long long, int, hipStream_t);
-void slab_reduce_launch(const SlabJob&, hipStream_t);
-void pe_proj_fwd_launch(const float*, int, const float*, const float*, const float*, const float*, const float*,
-                        const float*, long long, int, int, int, float, uint16_t*, float*, float*, hipStream_t);
-int pe_proj_bwd_blocks(int);
-void attn_fwd_pe_launch(const PeFwdArgs&, hipStream_t);
-int attn_fwd_pe_auto_splits(int, int, int);
-void attn_combine_launch(const float*, const float*, uint16_t*, float*, int, long long, int, hipStream_t);
-void attn_bwd_pe_launch(const PeBwdArgs&, int, int, hipStream_t);
-void pe_proj_bwd_launch(const float*, const float*, int, const float*, const float*, int, int, int, float*, float*,
-                        hipStream_t);
-}  // namespace pio
 
 using torch::Tensor;
 using OptT = c10::optional<Tensor>;
@@ -237,6 +59,9 @@ bool is_bf16(const Tensor& t) {
   TORCH_CHECK(t.scalar_type() == torch::kBFloat16 || t.scalar_type() == torch::kFloat32, "expected bf16/fp32");
   return t.scalar_type() == torch::kBFloat16;
 }
+float* f32p_mut(Tensor& t) { CHECK_DT(t, torch::kFloat32); return t.data_ptr<float>(); }
+// the rows of a 2-D fp32 / bf16 tensor with unit inner stride
+pio::RowsIn rows_in(const Tensor& t) { return pio::RowsIn{t.data_ptr(), is_bf16(t), (int)t.stride(0)}; }
 
 // 3-D (B|1, N, >=HD) view with unit inner stride → (batch stride, row stride)
 void strides3(const Tensor& t, int B, long long& bs, int& rs) {
@@ -248,7 +73,7 @@ void strides3(const Tensor& t, int B, long long& bs, int& rs) {
               "attention operands need 16-byte aligned rows");
 }
 
-// device dropout seed: a 1-element int64 GPU tensor (drawn per forward call, see common.h DropCfg)
+// device dropout seed: a 1-element int64 GPU tensor (drawn per forward call, see host_api.h DropCfg)
 const int64_t* seed_ptr(const OptT& seed, double p) {
   if (!(p > 0)) return nullptr;
   TORCH_CHECK(seed.has_value(), "dropout > 0 needs a device seed tensor");
@@ -377,20 +202,33 @@ std::vector<Tensor> attn_bwd(Tensor q, Tensor k, Tensor v, OptT kmask, Tensor o,
   } else {
     delta = torch::empty({a.B, a.Nq, H}, f32);
   }
+  auto rows3 = [](Tensor& t) { return pio::Rows3{t.data_ptr<float>(), t.stride(0), (int)t.stride(1)}; };
+  pio::AttnBwdArgs b{};
+  b.a = a;
+  b.O = bfp(o);
+  b.dO = bfp(dO);
+  b.LSE = f32p(lse);
+  b.delta = delta.data_ptr<float>();
+  b.dk = rows3(dk);
+  b.dv = rows3(dv);
+  b.compute_delta = !delta_in.has_value();
+  b.kv_acc = kv_accumulate;
   const int nkb = pio::attn_bwd_key_blocks(a.Nk, (int)D);
   if (g_det && nkb > 1) {  // one dQ partial slice per key block, summed in a fixed order
     Tensor part = torch::empty({nkb, a.B, a.Nq, H * D}, f32);
-    pio::attn_bwd_launch(a, (int)D, bfp(o), bfp(dO), f32p(lse), delta.data_ptr<float>(), part.data_ptr<float>(),
-                         (long long)a.Nq * H * D, (int)(H * D), dk.data_ptr<float>(), dk.stride(0), (int)dk.stride(1),
-                         dv.data_ptr<float>(), dv.stride(0), (int)dv.stride(1), !delta_in.has_value(), kv_accumulate,
-                         (long long)a.B * a.Nq * H * D, 0, 0, stream());
+    b.dq = pio::Rows3{part.data_ptr<float>(), (long long)a.Nq * H * D, (int)(H * D)};
+    b.dq_kbs = (long long)a.B * a.Nq * H * D;
+    b.qsplit_ok = 0;
+    b.dq_zeroed = 0;
+    pio::attn_bwd_launch(b, (int)D, stream());
     dq.narrow(2, 0, H * D).copy_(part.sum(0));
     return {dq, dk, dv};
   }
-  pio::attn_bwd_launch(a, (int)D, bfp(o), bfp(dO), f32p(lse), delta.data_ptr<float>(), dq.data_ptr<float>(),
-                       dq.stride(0), (int)dq.stride(1), dk.data_ptr<float>(), dk.stride(0), (int)dk.stride(1),
-                       dv.data_ptr<float>(), dv.stride(0), (int)dv.stride(1), !delta_in.has_value(), kv_accumulate, 0,
-                       g_det ? 0 : 1, (dq_zeroed ? 1 : 0) | (kv_zeroed ? 2 : 0), stream());
+  b.dq = rows3(dq);
+  b.dq_kbs = 0;
+  b.qsplit_ok = g_det ? 0 : 1;
+  b.dq_zeroed = (dq_zeroed ? 1 : 0) | (kv_zeroed ? 2 : 0);
+  pio::attn_bwd_launch(b, (int)D, stream());
   return {dq, dk, dv};
 }
 
@@ -399,24 +237,28 @@ std::vector<Tensor> attn_bwd(Tensor q, Tensor k, Tensor v, OptT kmask, Tensor o,
 // images) — with the pixels added into its npix leading (zero) columns; pe is (M, pe_rs) fp32
 // contiguous with pe_rs a multiple of 8, ≥ Kin = w.size(1)
 namespace {
-void pe_args(const OptT& pe, const Tensor& x, int R, int Kin, const float*& pp, int& prs, int& prows, int& npix,
-             const OptT& pe_index, const long long*& pidx) {
-  pp = nullptr; prs = 0; prows = 1; npix = 0; pidx = nullptr;
+pio::PeSplit pe_split(const OptT& pe, const Tensor& x, int R, int Kin, const OptT& pe_index) {
+  pio::PeSplit ps{};
+  ps.M = 1;
   TORCH_CHECK(!pe_index.has_value() || pe.has_value(), "pe_index needs a pe table");
-  if (!pe.has_value()) return;
+  if (!pe.has_value()) return ps;
   CHECK_DT(*pe, torch::kFloat32);
   TORCH_CHECK(pe->dim() == 2 && pe->is_contiguous() && pe->size(1) % 8 == 0 && pe->size(1) >= Kin,
               "pe must be (M, pe_rs) contiguous fp32, pe_rs a multiple of 8 and >= Kin");
   if (pe_index.has_value()) {
     CHECK_DT(*pe_index, torch::kInt64);
     TORCH_CHECK(pe_index->is_contiguous() && pe_index->numel() == R, "pe_index must be R contiguous int64 rows");
-    pidx = reinterpret_cast<const long long*>(pe_index->data_ptr<int64_t>());
+    ps.idx = reinterpret_cast<const long long*>(pe_index->data_ptr<int64_t>());
   } else {
     TORCH_CHECK(R % pe->size(0) == 0, "rows must be a multiple of the PE rows");
   }
   TORCH_CHECK(reinterpret_cast<uintptr_t>(pe->data_ptr()) % 16 == 0, "pe must be 16-byte aligned");
-  pp = pe->data_ptr<float>(); prs = (int)pe->size(1); prows = (int)pe->size(0); npix = (int)x.size(1);
-  TORCH_CHECK(npix <= Kin, "more pixel channels than inputs");
+  ps.pe = pe->data_ptr<float>();
+  ps.pe_rs = (int)pe->size(1);
+  ps.M = (int)pe->size(0);
+  ps.npix = (int)x.size(1);
+  TORCH_CHECK(ps.npix <= Kin, "more pixel channels than inputs");
+  return ps;
 }
 }  // namespace
 
@@ -430,25 +272,34 @@ std::vector<Tensor> ln_linear_fwd(Tensor x, OptT lnw, OptT lnb, double eps, Tens
   TORCH_CHECK(w.dim() == 2 && w.is_contiguous() && w.size(1) >= Kin, "w must be (N, >= Kin) contiguous");
   TORCH_CHECK(pe.has_value() || x.size(1) == Kin, "x must be (R, Kin)");
   TORCH_CHECK(Kin <= 256, "Kin > 256 unsupported");
-  const float* pp; int prs, prows, npix; const long long* pidx;
-  pe_args(pe, x, R, Kin, pp, prs, prows, npix, pe_index, pidx);
+  pio::LnLinearFwdArgs a{};
+  a.ps = pe_split(pe, x, R, Kin, pe_index);
   auto opts = x.options();
   Tensor y = torch::empty({R, N}, opts.dtype(out_bf16 ? torch::kBFloat16 : torch::kFloat32));
   Tensor mean, rstd;
-  float *mp = nullptr, *rp = nullptr;
   if (save_stats && lnw.has_value()) {
     mean = torch::empty({R}, opts.dtype(torch::kFloat32));
     rstd = torch::empty({R}, opts.dtype(torch::kFloat32));
-    mp = mean.data_ptr<float>(); rp = rstd.data_ptr<float>();
+    a.mean = mean.data_ptr<float>();
+    a.rstd = rstd.data_ptr<float>();
   }
-  const float* rptr = nullptr; int res_rs = 0;
-  if (res.has_value()) { rptr = f32p(*res); res_rs = (int)res->stride(0); TORCH_CHECK(res->stride(1) == 1); }
-  pio::ln_linear_fwd_launch(x.data_ptr(), is_bf16(x), (int)x.stride(0), R, Kin, f32o(lnw), f32o(lnb), (float)eps, bfp(w),
-                            (int)w.size(1), f32o(bias), N, (int)act, rptr, res_rs, y.data_ptr(), out_bf16, N, mp, rp, pp, prs, prows,
-                            npix, pidx, stream());
-  if (pidx) checked_sync("ln_linear_fwd (pe_index)");
+  if (res.has_value()) { a.res = f32p(*res); a.res_rs = (int)res->stride(0); TORCH_CHECK(res->stride(1) == 1); }
+  a.X = rows_in(x);
+  a.R = R;
+  a.Kin = Kin;
+  a.lnw = f32o(lnw);
+  a.lnb = f32o(lnb);
+  a.eps = (float)eps;
+  a.W = bfp(w);
+  a.w_rs = (int)w.size(1);
+  a.bias = f32o(bias);
+  a.N = N;
+  a.act = (int)act;
+  a.Y = pio::RowsOut{y.data_ptr(), out_bf16, N};
+  pio::ln_linear_fwd_launch(a, stream());
+  if (a.ps.idx) checked_sync("ln_linear_fwd (pe_index)");
   std::vector<Tensor> out{y};
-  if (mp) { out.push_back(mean); out.push_back(rstd); }
+  if (a.mean) { out.push_back(mean); out.push_back(rstd); }
   return out;
 }
 
@@ -462,9 +313,27 @@ std::vector<Tensor> post_attn_fwd(Tensor o, Tensor x, Tensor wo, Tensor bo, Tens
   Tensor z = torch::empty({R, C}, f32), y = torch::empty({R, C}, f32);
   Tensor m = torch::empty({R}, f32), r = torch::empty({R}, f32);
   Tensor u = torch::empty({R, C}, x.options().dtype(torch::kBFloat16));
-  pio::post_attn_fwd_launch(C, bfp(o), f32p(x), bfp(wo), f32p(bo), f32p(g2), f32p(be2), (float)eps, bfp(w1), f32p(b1),
-                            bfp(w2), f32p(b2), z.data_ptr<float>(), y.data_ptr<float>(), m.data_ptr<float>(),
-                            r.data_ptr<float>(), bfp_mut(u), R, Rx, make_drop(seed, site, p), stream());
+  pio::PostAttnFwdArgs a{};
+  a.O = bfp(o);
+  a.X = f32p(x);
+  a.p.Wo = bfp(wo);
+  a.p.bo = f32p(bo);
+  a.p.g2 = f32p(g2);
+  a.p.be2 = f32p(be2);
+  a.p.eps = (float)eps;
+  a.p.W1 = bfp(w1);
+  a.p.b1 = f32p(b1);
+  a.p.W2 = bfp(w2);
+  a.p.b2 = f32p(b2);
+  a.Z = z.data_ptr<float>();
+  a.s.Ysave = y.data_ptr<float>();
+  a.s.mean2 = m.data_ptr<float>();
+  a.s.rstd2 = r.data_ptr<float>();
+  a.s.Usave = bfp_mut(u);
+  a.R = R;
+  a.Rx = Rx;
+  a.dr = make_drop(seed, site, p);
+  pio::post_attn_fwd_launch(a, C, stream());
   return {z, y, m, r, u};
 }
 
@@ -486,11 +355,35 @@ std::vector<Tensor> post_attn_ln_linear_fwd(Tensor o, Tensor x, Tensor wo, Tenso
   Tensor z = torch::empty({R, C}, f32), y = torch::empty({R, C}, f32);
   Tensor m = torch::empty({R}, f32), r = torch::empty({R}, f32), u = torch::empty({R, C}, b16);
   Tensor qkv = torch::empty({R, 3 * C}, b16), m1 = torch::empty({R}, f32), r1 = torch::empty({R}, f32);
-  pio::post_attn_ln_linear_fwd_launch(C, bfp(o), f32p(x), bfp(wo), f32p(bo), f32p(g2), f32p(be2), (float)eps, bfp(w1),
-                                      f32p(b1), bfp(w2), f32p(b2), z.data_ptr<float>(), y.data_ptr<float>(),
-                                      m.data_ptr<float>(), r.data_ptr<float>(), bfp_mut(u), R, Rx, f32p(lnw), f32p(lnb),
-                                      bfp(wq), f32p(bq), bfp_mut(qkv), m1.data_ptr<float>(), r1.data_ptr<float>(),
-                                      make_drop(seed, site, p), stream());
+  pio::PostAttnFwdArgs a{};
+  a.O = bfp(o);
+  a.X = f32p(x);
+  a.p.Wo = bfp(wo);
+  a.p.bo = f32p(bo);
+  a.p.g2 = f32p(g2);
+  a.p.be2 = f32p(be2);
+  a.p.eps = (float)eps;
+  a.p.W1 = bfp(w1);
+  a.p.b1 = f32p(b1);
+  a.p.W2 = bfp(w2);
+  a.p.b2 = f32p(b2);
+  a.Z = z.data_ptr<float>();
+  a.s.Ysave = y.data_ptr<float>();
+  a.s.mean2 = m.data_ptr<float>();
+  a.s.rstd2 = r.data_ptr<float>();
+  a.s.Usave = bfp_mut(u);
+  a.R = R;
+  a.Rx = Rx;
+  a.next.lnw = f32p(lnw);
+  a.next.lnb = f32p(lnb);
+  a.next.Wq = bfp(wq);
+  a.next.bq = f32p(bq);
+  a.next.QKVn = bfp_mut(qkv);
+  a.next.mean1 = m1.data_ptr<float>();
+  a.next.rstd1 = r1.data_ptr<float>();
+  a.next.nq = 3 * C;
+  a.dr = make_drop(seed, site, p);
+  pio::post_attn_ln_linear_fwd_launch(a, C, stream());
   return {z, y, m, r, u, qkv, m1, r1};
 }
 
@@ -521,14 +414,40 @@ std::vector<Tensor> sa_layer_fwd(Tensor qkv, Tensor x, int64_t N, double scale, 
   Tensor m = torch::empty({R}, f32), r = torch::empty({R}, f32), u = torch::empty({R, C}, b16);
   Tensor qn, m1, r1;
   if (next) { qn = torch::empty({R, nq}, b16); m1 = torch::empty({R}, f32); r1 = torch::empty({R}, f32); }
-  const bool launched = pio::sa_layer_fwd_launch(bfp(qkv), (int)N, (float)(scale * 1.4426950408889634), bfp_mut(o), lse.data_ptr<float>(),
-                           f32p(x), bfp(wo), f32p(bo), f32p(g2), f32p(be2), (float)eps, bfp(w1), f32p(b1), bfp(w2),
-                           f32p(b2), z.data_ptr<float>(), y.data_ptr<float>(), m.data_ptr<float>(), r.data_ptr<float>(),
-                           bfp_mut(u), R, next ? f32p(*lnw) : nullptr, next ? f32p(*lnb) : nullptr,
-                           next ? bfp(*wq) : nullptr, next ? f32p(*bq) : nullptr, next ? bfp_mut(qn) : nullptr,
-                           next ? m1.data_ptr<float>() : nullptr, next ? r1.data_ptr<float>() : nullptr,
-                           make_drop(seed, site, p), nq, stream());
-  TORCH_CHECK(launched, "sa_layer_fwd: every operand must be 16-byte aligned");
+  pio::SaLayerFwdArgs a{};
+  a.QKV = bfp(qkv);
+  a.N = (int)N;
+  a.scale_log2 = (float)(scale * 1.4426950408889634);
+  a.O = bfp_mut(o);
+  a.LSE = lse.data_ptr<float>();
+  a.X = f32p(x);
+  a.p.Wo = bfp(wo);
+  a.p.bo = f32p(bo);
+  a.p.g2 = f32p(g2);
+  a.p.be2 = f32p(be2);
+  a.p.eps = (float)eps;
+  a.p.W1 = bfp(w1);
+  a.p.b1 = f32p(b1);
+  a.p.W2 = bfp(w2);
+  a.p.b2 = f32p(b2);
+  a.Z = z.data_ptr<float>();
+  a.s.Ysave = y.data_ptr<float>();
+  a.s.mean2 = m.data_ptr<float>();
+  a.s.rstd2 = r.data_ptr<float>();
+  a.s.Usave = bfp_mut(u);
+  a.R = R;
+  if (next) {
+    a.next.lnw = f32p(*lnw);
+    a.next.lnb = f32p(*lnb);
+    a.next.Wq = bfp(*wq);
+    a.next.bq = f32p(*bq);
+    a.next.QKVn = bfp_mut(qn);
+    a.next.mean1 = m1.data_ptr<float>();
+    a.next.rstd1 = r1.data_ptr<float>();
+  }
+  a.next.nq = nq;
+  a.dr = make_drop(seed, site, p);
+  TORCH_CHECK(pio::sa_layer_fwd_launch(a, stream()), "sa_layer_fwd: every operand must be 16-byte aligned");
   if (next) return {o, lse, z, y, m, r, u, qn, m1, r1};
   return {o, lse, z, y, m, r, u};
 }
@@ -1009,10 +928,27 @@ std::vector<Tensor> post_attn_bwd(Tensor dz, Tensor y, Tensor m2, Tensor r2, Ten
   Tensor dy = torch::empty({R, C}, f32);
   Tensor dO = torch::empty({R, C}, dz.options().dtype(torch::kBFloat16));
   Tensor delta = torch::empty({R, H}, f32);
-  pio::SlabJob job = with_zero_span(make_job(job_slab, job_dsts, job_offs), zero_out, dz);
-  pio::post_attn_bwd_launch(C, f32p(dz), f32p(y), f32p(m2), f32p(r2), bfp(u), bfp(o), bfp(wo), bfp(w1), bfp(w2),
-                            f32p(g2), f32p(be2), dy.data_ptr<float>(), bfp_mut(dO), delta.data_ptr<float>(), (int)H,
-                            pg, R, job, make_drop(seed, site, p), stream());
+  pio::PostAttnBwdArgs a{};
+  a.dZ = f32p(dz);
+  a.s.Ysave = f32p_mut(y);
+  a.s.mean2 = f32p_mut(m2);
+  a.s.rstd2 = f32p_mut(r2);
+  a.s.Usave = bfp_mut(u);
+  a.O = bfp(o);
+  a.p.Wo = bfp(wo);
+  a.p.W1 = bfp(w1);
+  a.p.W2 = bfp(w2);
+  a.p.g2 = f32p(g2);
+  a.p.be2 = f32p(be2);
+  a.dY = dy.data_ptr<float>();
+  a.dO = bfp_mut(dO);
+  a.delta = delta.data_ptr<float>();
+  a.H = (int)H;
+  a.grads = pg;
+  a.R = R;
+  a.job = with_zero_span(make_job(job_slab, job_dsts, job_offs), zero_out, dz);
+  a.dr = make_drop(seed, site, p);
+  pio::post_attn_bwd_launch(a, C, stream());
   return {dy, dO, delta};
 }
 
@@ -1053,12 +989,40 @@ std::vector<Tensor> ln_linear_post_attn_bwd(Tensor g, Tensor wq, Tensor x, Tenso
   Tensor dy = torch::empty({R, C}, f32);
   Tensor dO = torch::empty({R, C}, y.options().dtype(torch::kBFloat16));
   Tensor delta = torch::empty({R, H}, f32);
-  const auto job = with_zero_span(make_job(job_slab, job_dsts, job_offs), zero_out, y);
-  const auto dr = make_drop(seed, site, p);
+  pio::LnLinearPostAttnBwdArgs a{};
+  a.next.Wq = bfp(wq);
+  a.next.lnw = f32p(lnw);
+  a.next.lnb = f32p(lnb);
+  a.next.mean1 = f32p_mut(mean1);
+  a.next.rstd1 = f32p_mut(rstd1);
+  a.next.nq = nq;
+  a.X = f32p(x);
+  a.dres = f32p(dres);
+  a.dlnw = dg1;
+  a.dlnb = db1;
+  a.dWq = dwq;
+  a.dbq = dbq;
+  a.pa.s.Ysave = f32p_mut(y);
+  a.pa.s.mean2 = f32p_mut(m2);
+  a.pa.s.rstd2 = f32p_mut(r2);
+  a.pa.s.Usave = bfp_mut(u);
+  a.pa.O = bfp(o);
+  a.pa.p.Wo = bfp(wo);
+  a.pa.p.W1 = bfp(w1);
+  a.pa.p.W2 = bfp(w2);
+  a.pa.p.g2 = f32p(g2);
+  a.pa.p.be2 = f32p(be2);
+  a.pa.dY = dy.data_ptr<float>();
+  a.pa.dO = bfp_mut(dO);
+  a.pa.delta = delta.data_ptr<float>();
+  a.pa.H = (int)H;
+  a.pa.grads = pg;
+  a.pa.R = R;
+  a.pa.job = with_zero_span(make_job(job_slab, job_dsts, job_offs), zero_out, y);
+  a.pa.dr = make_drop(seed, site, p);
   // att_*: the layer below's attention backward fused in (N = 64 latents per sample, the tile is
   // the sample): its packed QKV rows and LSE in, its dQKV (R, 3C) bf16 out; dO / delta are then
   // not produced (the returned tensors are unwritten)
-  const uint16_t* aq = nullptr; const float* al = nullptr; uint16_t* ao = nullptr;
   if (att_out.has_value()) {
     TORCH_CHECK(att_qkv.has_value() && att_lse.has_value(), "att_out needs att_qkv and att_lse");
     CHECK_DT(*att_qkv, torch::kBFloat16); CHECK_DT(*att_out, torch::kBFloat16); CHECK_DT(*att_lse, torch::kFloat32);
@@ -1066,19 +1030,19 @@ std::vector<Tensor> ln_linear_post_attn_bwd(Tensor g, Tensor wq, Tensor x, Tenso
     TORCH_CHECK(att_qkv->is_contiguous() && att_qkv->numel() == (int64_t)R * 3 * C && att_out->is_contiguous() &&
                     att_out->numel() == (int64_t)R * 3 * C && att_lse->is_contiguous() && att_lse->numel() == (int64_t)R * H,
                 "fused attention backward: qkv / out (R, 3C), lse (R, H) contiguous");
-    aq = bfp(*att_qkv); al = f32p(*att_lse); ao = bfp_mut(*att_out);
+    a.att.qkv = bfp(*att_qkv);
+    a.att.lse = f32p(*att_lse);
+    a.att.out = bfp_mut(*att_out);
   }
+  a.att.scale = (float)att_scale;
   auto launch = [&](const Tensor& gg) {
-    const bool gbf = gg.scalar_type() == torch::kBFloat16;
-    return pio::ln_linear_post_attn_bwd_launch(
-        C, gg.data_ptr(), gbf, bfp(wq), f32p(x), f32p(mean1), f32p(rstd1), f32p(lnw), f32p(lnb), f32p(dres), dg1, db1,
-        dwq, dbq, f32p(y), f32p(m2), f32p(r2), bfp(u), bfp(o), bfp(wo), bfp(w1), bfp(w2), f32p(g2), f32p(be2),
-        dy.data_ptr<float>(), bfp_mut(dO), delta.data_ptr<float>(), (int)H, pg, R, job, dr, nq, aq, al, ao,
-        (float)att_scale, stream());
+    a.G = gg.data_ptr();
+    a.g_bf16 = gg.scalar_type() == torch::kBFloat16;
+    return pio::ln_linear_post_attn_bwd_launch(a, C, stream());
   };
   // a bf16 G (from attn_bwd's bf16 outputs) is taken by the chain-layout kernel; any other
   // kernel gets it widened to fp32 (same values)
-  if (!launch(g)) TORCH_CHECK(!ao && launch(g.to(torch::kFloat32)), "ln_linear_post_attn_bwd: launch failed");
+  if (!launch(g)) TORCH_CHECK(!a.att.out && launch(g.to(torch::kFloat32)), "ln_linear_post_attn_bwd: launch failed");
   return {dy, dO, delta};
 }
 
@@ -1099,8 +1063,7 @@ OptT ln_linear_bwd(Tensor g, Tensor w, Tensor x, OptT mean, OptT rstd, OptT lnw,
   TORCH_CHECK(w.size(0) == N && w.is_contiguous() && w.size(1) >= Kin, "w must be (N, >= Kin) contiguous, N = g columns");
   TORCH_CHECK(x.size(0) == R && (pe.has_value() || x.size(1) == Kin), "x must be (R, Kin)");
   TORCH_CHECK(!(pe.has_value() && need_dx), "no input gradient for a split (pixels + PE) input");
-  const float* pp; int prs, prows, npix; const long long* pidx;
-  pe_args(pe, x, R, Kin, pp, prs, prows, npix, pe_index, pidx);
+  const pio::PeSplit ps = pe_split(pe, x, R, Kin, pe_index);
   TORCH_CHECK(Kin <= 160, "ln_linear_bwd supports Kin <= 160");
   auto f32 = g.options().dtype(torch::kFloat32);
   Tensor dx;
@@ -1127,20 +1090,54 @@ OptT ln_linear_bwd(Tensor g, Tensor w, Tensor x, OptT mean, OptT rstd, OptT lnw,
   if (dW.has_value()) dwp = vec_target(*dW, (int64_t)N * Kin, "dW", wrs, sr);
   if (db.has_value()) { TORCH_CHECK(dW.has_value(), "db needs dW"); dbiasp = vec_target(*db, N, "db", vrs, sr); }
   TORCH_CHECK(!slab || vrs < 0 || wrs < 0 || vrs == wrs, "slab targets must share one slab");
-  const float* dr = nullptr; int drs = 0;
-  if (dres.has_value()) { dr = f32p(*dres); drs = (int)dres->stride(0); TORCH_CHECK(dres->stride(1) == 1); }
   // very tall inputs (image K/V projections): the weight gradient leaves the row-tile kernel
   // for the streaming tall-wgrad kernel (one partial per ~R/128 rows instead of per 64)
   const bool tall = dwp != nullptr && R >= kTallRows;
-  pio::ln_linear_bwd_launch(g.data_ptr(), is_bf16(g), (int)g.stride(0), N, bfp(w), (int)w.size(1), Kin, x.data_ptr(),
-                            is_bf16(x), (int)x.stride(0), f32o(mean), f32o(rstd), f32o(lnw), f32o(lnb), dr, drs, dxp,
-                            dx_rs, dgp, dbp, tall ? nullptr : dwp, tall ? nullptr : dbiasp, vrs < 0 ? 0 : vrs,
-                            wrs < 0 ? 0 : wrs, slab ? 1 : 0, R, pp, prs, prows, npix, pidx,
-                            make_job(job_slab, job_dsts, job_offs), stream());
-  if (tall)
-    pio::wgrad_launch(g.data_ptr(), is_bf16(g), (int)g.stride(0), N, x.data_ptr(), is_bf16(x), (int)x.stride(0), Kin,
-                      lnw.has_value() ? 1 : 0, f32o(mean), f32o(rstd), f32o(lnw), f32o(lnb), R, 0, dwp, dbiasp,
-                      vrs < 0 ? 0 : vrs, wrs < 0 ? 0 : wrs, pp, prs, prows, npix, pidx, stream());
+  pio::LnLinearBwdArgs a{};
+  a.G = rows_in(g);
+  a.N = N;
+  a.W = bfp(w);
+  a.w_rs = (int)w.size(1);
+  a.Kin = Kin;
+  a.X = rows_in(x);
+  a.mean = f32o(mean);
+  a.rstd = f32o(rstd);
+  a.lnw = f32o(lnw);
+  a.lnb = f32o(lnb);
+  if (dres.has_value()) { a.dres = f32p(*dres); a.dres_rs = (int)dres->stride(0); TORCH_CHECK(dres->stride(1) == 1); }
+  a.dX = dxp;
+  a.dx_rs = dx_rs;
+  a.dlnw = dgp;
+  a.dlnb = dbp;
+  a.dW = tall ? nullptr : dwp;
+  a.db = tall ? nullptr : dbiasp;
+  a.vrs = vrs < 0 ? 0 : vrs;
+  a.wrs = wrs < 0 ? 0 : wrs;
+  a.slab = slab ? 1 : 0;
+  a.R = R;
+  a.ps = ps;
+  a.job = make_job(job_slab, job_dsts, job_offs);
+  pio::ln_linear_bwd_launch(a, stream());
+  if (tall) {
+    pio::WgradArgs wa{};
+    wa.G = a.G;
+    wa.N = N;
+    wa.A = a.X;
+    wa.Kin = Kin;
+    wa.amode = lnw.has_value() ? 1 : 0;
+    wa.mean = a.mean;
+    wa.rstd = a.rstd;
+    wa.lnw = a.lnw;
+    wa.lnb = a.lnb;
+    wa.R = R;
+    wa.rows_per_wg = 0;
+    wa.dW = dwp;
+    wa.db = dbiasp;
+    wa.vrs = a.vrs;
+    wa.wrs = a.wrs;
+    wa.ps = ps;
+    pio::wgrad_launch(wa, stream());
+  }
   if (need_dx) return dx;
   return c10::nullopt;
 }
@@ -1157,14 +1154,25 @@ void wgrad(Tensor g, Tensor a, int64_t amode, OptT mean, OptT rstd, OptT lnw, Op
   TORCH_CHECK(!g_det, "deterministic mode: the streaming wgrad kernel adds partials with atomics");
   TORCH_CHECK(amode != 1 || (mean.has_value() && rstd.has_value() && lnw.has_value() && lnb.has_value()),
               "LN mode needs stats and affine");
-  const float* pp; int prs, prows, npix; const long long* pidx;
-  pe_args(pe, a, R, Kin, pp, prs, prows, npix, pe_index, pidx);
+  pio::WgradArgs wa{};
+  wa.ps = pe_split(pe, a, R, Kin, pe_index);
   int wrs = -1, vrs = -1;
-  float* dwp = vec_target(dW, (int64_t)N * Kin, "dW", wrs);
-  float* dbp = db.has_value() ? vec_target(*db, N, "db", vrs) : nullptr;
-  pio::wgrad_launch(g.data_ptr(), is_bf16(g), (int)g.stride(0), N, a.data_ptr(), is_bf16(a), (int)a.stride(0), Kin,
-                    (int)amode, f32o(mean), f32o(rstd), f32o(lnw), f32o(lnb), R, (int)rows_per_wg, dwp, dbp,
-                    vrs < 0 ? 0 : vrs, wrs < 0 ? 0 : wrs, pp, prs, prows, npix, pidx, stream());
+  wa.dW = vec_target(dW, (int64_t)N * Kin, "dW", wrs);
+  wa.db = db.has_value() ? vec_target(*db, N, "db", vrs) : nullptr;
+  wa.vrs = vrs < 0 ? 0 : vrs;
+  wa.wrs = wrs < 0 ? 0 : wrs;
+  wa.G = rows_in(g);
+  wa.N = N;
+  wa.A = rows_in(a);
+  wa.Kin = Kin;
+  wa.amode = (int)amode;
+  wa.mean = f32o(mean);
+  wa.rstd = f32o(rstd);
+  wa.lnw = f32o(lnw);
+  wa.lnb = f32o(lnb);
+  wa.R = R;
+  wa.rows_per_wg = (int)rows_per_wg;
+  pio::wgrad_launch(wa, stream());
 }
 
 // per-device ticket of the CE combine kernel (its last workgroup sums the per-block partials):
@@ -2202,11 +2210,6 @@ void set_deterministic(bool on) { g_det = on; }
 bool get_deterministic() { return g_det; }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
-  TORCH_CHECK(pio::abi_struct_size(0) == (int)sizeof(pio::DropCfg) &&
-                  pio::abi_struct_size(1) == (int)sizeof(pio::PostAttnGrads) &&
-                  pio::abi_struct_size(2) == (int)sizeof(pio::SlabJob) &&
-                  pio::abi_struct_size(3) == (int)sizeof(pio::AttnArgs),
-              "perceiver_io_amd: binding.cpp struct mirrors disagree with the kernels (csrc/common.h, attention.hip)");
   m.def("set_deterministic", &set_deterministic);
   m.def("check_errors", &check_errors, py::arg("reset") = true);
   m.def("checked_build", &checked_build);

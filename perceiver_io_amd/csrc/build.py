@@ -23,6 +23,10 @@ PKG = HERE.parent
 BUILD = PKG.parent / "build" / "csrc"
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+# every *.hip translation unit (plus its PER_FILE_FLAGS, the optimisation level and, for the
+# checked variant, -DPIO_CHECKS=1)
+HIP_FLAGS = [f"--offload-arch={ARCH}", "-fPIC", "-std=c++17", "-ffp-contract=fast", "-munsafe-fp-atomics",
+             "-Wno-unused-result"]
 
 
 # MFMA results in VGPRs (no AGPR staging) for the translation units whose kernels post-process
@@ -76,8 +80,7 @@ def build(force: bool = False, jobs: int = 0, debug: bool = False, verbose: bool
     headers = sorted(HERE.glob("*.h"))
     hip_srcs = sorted(HERE.glob("*.hip"))
     opt = ["-O0", "-g"] if debug else ["-O3"]
-    hip_flags = [f"--offload-arch={ARCH}", "-fPIC", "-std=c++17", "-ffp-contract=fast", "-munsafe-fp-atomics",
-                 "-Wno-unused-result"] + opt + (["-DPIO_CHECKS=1"] if check else [])
+    hip_flags = HIP_FLAGS + opt + (["-DPIO_CHECKS=1"] if check else [])
     objs = []
     todo = []
     for src in hip_srcs:
@@ -95,9 +98,9 @@ def build(force: bool = False, jobs: int = 0, debug: bool = False, verbose: bool
                  *san,
                  "-isystem", "/opt/rocm/include", "-isystem", py_inc] + sum((["-isystem", p] for p in inc), [])
     bsrc = HERE / "binding.cpp"
-    # binding.cpp includes common.h (SlabJob, DropCfg, … are passed by value to the launchers):
-    # its object must be rebuilt when a header changes, or the host and the kernels disagree on
-    # a struct layout
+    # binding.cpp includes host_api.h (and through it the *_args.h headers), whose structs the
+    # kernels take by value: its object must be rebuilt when a header changes, or the host and
+    # the kernels disagree on a struct layout
     bobj = bdir / f"binding.{_digest([bsrc] + headers, cxx_flags)}.o"
     if force or not bobj.exists():
         todo.append(["g++", *cxx_flags, "-c", str(bsrc), "-o", str(bobj)])

@@ -724,36 +724,32 @@ __global__ __launch_bounds__(512) void ln_linear_post_attn_bwd_chain8_kernel(
 
 // ---- launchers (called by rowgemm.hip's launchers once the operands qualify: C = 64, H = 4,
 // every pointer 16-byte aligned, R % 64 == 0) ----
-bool sa_layer_fwd_chain_launch(const uint16_t* QKV, int N, float scale_log2, uint16_t* O, float* LSE, const float* X,
-                               const uint16_t* Wo, const float* bo, const float* g2, const float* be2, float eps,
-                               const uint16_t* W1, const float* b1, const uint16_t* W2, const float* b2, float* Z,
-                               float* Ysave, float* mean2, float* rstd2, uint16_t* Usave, int R, const float* lnw,
-                               const float* lnb, const uint16_t* Wq, const float* bq, uint16_t* QKVn, float* mean1,
-                               float* rstd1, const DropCfg& dr, int nq, hipStream_t st) {
-  const bool next = Wq != nullptr;
-  if (next && nq != 64 && nq != 128 && nq != 192) return false;
-  if (N > 512) return false;
-  dim3 grid(R / 64);
-#define SAC(NX, NQ, KT)                                                                                                  \
-  if (dr.thresh)                                                                                                         \
-    hipLaunchKernelGGL((sa_layer_fwd_chain8_kernel<NX, NQ, KT, true>), grid, dim3(512), 0, st, QKV, N, scale_log2, O, LSE, \
-                       X, Wo, bo, g2, be2, eps, W1, b1, W2, b2, Z, Ysave, mean2, rstd2, Usave, R, lnw, lnb, Wq, bq, QKVn,  \
-                       mean1, rstd1, dr);                                                                                \
-  else                                                                                                                   \
-    hipLaunchKernelGGL((sa_layer_fwd_chain8_kernel<NX, NQ, KT, false>), grid, dim3(512), 0, st, QKV, N, scale_log2, O,    \
-                       LSE, X, Wo, bo, g2, be2, eps, W1, b1, W2, b2, Z, Ysave, mean2, rstd2, Usave, R, lnw, lnb, Wq, bq,  \
-                       QKVn, mean1, rstd1, dr)
+bool sa_layer_fwd_chain_launch(const SaLayerFwdArgs& a, hipStream_t st) {
+  const PostAttnParams& p = a.p;
+  const PostAttnSaved& s = a.s;
+  const NextProj& n = a.next;
+  const bool next = n.Wq != nullptr;
+  if (next && n.nq != 64 && n.nq != 128 && n.nq != 192) return false;
+  if (a.N > 512) return false;
+  dim3 grid(a.R / 64);
+#define SAC(NX, NQ, KT)                                                                                              \
+  {                                                                                                                  \
+    auto fn = a.dr.thresh ? sa_layer_fwd_chain8_kernel<NX, NQ, KT, true> : sa_layer_fwd_chain8_kernel<NX, NQ, KT, false>; \
+    hipLaunchKernelGGL(fn, grid, dim3(512), 0, st, a.QKV, a.N, a.scale_log2, a.O, a.LSE, a.X, p.Wo, p.bo, p.g2, p.be2,  \
+                       p.eps, p.W1, p.b1, p.W2, p.b2, a.Z, s.Ysave, s.mean2, s.rstd2, s.Usave, a.R, n.lnw, n.lnb, n.Wq, \
+                       n.bq, n.QKVn, n.mean1, n.rstd1, a.dr);                                                        \
+  }
 #define SAK(KT)              \
   if (!next) {               \
-    SAC(false, 3, KT);       \
-  } else if (nq == 64) {     \
-    SAC(true, 1, KT);        \
-  } else if (nq == 128) {    \
-    SAC(true, 2, KT);        \
+    SAC(false, 3, KT)        \
+  } else if (n.nq == 64) {   \
+    SAC(true, 1, KT)         \
+  } else if (n.nq == 128) {  \
+    SAC(true, 2, KT)         \
   } else {                   \
-    SAC(true, 3, KT);        \
+    SAC(true, 3, KT)         \
   }
-  if (N <= 256) {
+  if (a.N <= 256) {
     SAK(8)
   } else {
     SAK(16)
@@ -763,30 +759,27 @@ bool sa_layer_fwd_chain_launch(const uint16_t* QKV, int N, float scale_log2, uin
   return true;
 }
 
-bool ln_linear_post_attn_bwd_chain_launch(const void* G, bool g_bf16, const uint16_t* Wq, const float* X, const float* mean1,
-                                          const float* rstd1, const float* lnw, const float* lnb, const float* dres,
-                                          float* dlnw, float* dlnb, float* dWq, float* dbq, const float* Ysave,
-                                          const float* mean2, const float* rstd2, const uint16_t* U, const uint16_t* O,
-                                          const uint16_t* Wo, const uint16_t* W1, const uint16_t* W2, const float* g2,
-                                          const float* be2, float* dY, uint16_t* dO, float* delta,
-                                          const PostAttnGrads& grads, int R, const SlabJob& job, const DropCfg& dr,
-                                          int nq, const uint16_t* att_qkv, const float* att_lse, uint16_t* att_out,
-                                          float att_scale, hipStream_t st) {
-  if (nq != 192 && nq != 64) return false;
+bool ln_linear_post_attn_bwd_chain_launch(const LnLinearPostAttnBwdArgs& a, hipStream_t st) {
+  const PostAttnBwdArgs& b = a.pa;
+  const PostAttnParams& p = b.p;
+  const PostAttnSaved& s = b.s;
+  const NextProj& n = a.next;
+  if (n.nq != 192 && n.nq != 64) return false;
   // phase D (att): layer l is a self-attention layer in both forms — NQ = 3 (layer l+1 a
   // self-attention layer too) and NQ = 1 (layer l+1 the next cross-attention layer's query path)
-  const bool att = att_out != nullptr;
-  dim3 grid((R + 63) / 64 + (job.slab ? job.nblk : 0));
-  const ChainAttn at{att_qkv, att_lse, att_out, att_scale, att_scale * 1.4426950408889634f};
-#define LPC(NQ, TG, A)                                                                                                   \
-  hipLaunchKernelGGL((ln_linear_post_attn_bwd_chain8_kernel<NQ, TG, A>), grid, dim3(512), 0, st, static_cast<const TG*>(G), \
-                     Wq, X, mean1, rstd1, lnw, lnb, dres, dlnw, dlnb, dWq, dbq, Ysave, mean2, rstd2, U, O, Wo, W1, W2,       \
-                     g2, be2, dY, dO, delta, grads, R, job, dr, at)
-  if (g_bf16) {
-    if (nq != 192) return false;  // bf16 G only from the self-attention backward (nq = 3C)
+  const bool att = a.att.out != nullptr;
+  dim3 grid((b.R + 63) / 64 + (b.job.slab ? b.job.nblk : 0));
+  const ChainAttn at{a.att.qkv, a.att.lse, a.att.out, a.att.scale, a.att.scale * 1.4426950408889634f};
+#define LPC(NQ, TG, A)                                                                                                 \
+  hipLaunchKernelGGL((ln_linear_post_attn_bwd_chain8_kernel<NQ, TG, A>), grid, dim3(512), 0, st,                       \
+                     static_cast<const TG*>(a.G), n.Wq, a.X, n.mean1, n.rstd1, n.lnw, n.lnb, a.dres, a.dlnw, a.dlnb,   \
+                     a.dWq, a.dbq, s.Ysave, s.mean2, s.rstd2, s.Usave, b.O, p.Wo, p.W1, p.W2, p.g2, p.be2, b.dY, b.dO, \
+                     b.delta, b.grads, b.R, b.job, b.dr, at)
+  if (a.g_bf16) {
+    if (n.nq != 192) return false;  // bf16 G only from the self-attention backward (nq = 3C)
     if (att) LPC(3, uint16_t, true);
     else LPC(3, uint16_t, false);
-  } else if (nq == 192) {
+  } else if (n.nq == 192) {
     if (att) LPC(3, float, true);
     else LPC(3, float, false);
   } else if (att) {

@@ -13,6 +13,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "host_api.h"
+
 namespace pio {
 
 // ---- checked builds (python -m perceiver_io_amd.csrc.build --check → _C_check) ------------
@@ -253,7 +255,7 @@ __device__ int trace_bx, trace_by, trace_bz;
 // Reduction block (x, y): 256 columns × slab rows [32y, 32y + 32); wave w sums rows w, w+4, …
 // (all loads in flight), LDS combine, then wave w adds columns 64w..64w+63 with one
 // contiguous 256-B no-return atomic instruction: S/32 adds per element in all.
-constexpr int kMaxSlabSegs = 16;
+// (SlabJob itself: host_api.h)
 
 // 32 bytes of zeros in global memory: the source of every out-of-range element of a fetch.  A
 // load whose predicate is false reads here instead (an address select), so a phase's loads
@@ -278,20 +280,6 @@ __device__ __forceinline__ void lds_sync() {
   asm volatile("" ::: "memory");
 }
 
-struct SlabJob {
-  const float* slab;  // nullptr: no job
-  int S, P, nbx, nblk;
-  int det;            // deterministic mode: one block per column range sums ALL rows, plain add
-  int n;
-  float* dst[kMaxSlabSegs];
-  int off[kMaxSlabSegs];
-  int len[kMaxSlabSegs];
-  // side job of the kernel that carries this struct: clear zero_n4 float4s at zero_p (the
-  // accumulator of the NEXT kernel, e.g. the attention backward's atomic dQ), one slice per
-  // workgroup — no separate fill launch on the chain
-  float* zero_p;
-  long long zero_n4;
-};
 // this workgroup's slice of a SlabJob zero span
 __device__ __forceinline__ void zero_span_block(const SlabJob& j) {
   if (j.zero_p == nullptr) return;
@@ -308,9 +296,6 @@ __device__ __forceinline__ void zero_span_block(const SlabJob& j) {
 // kernel (≈100 KB of LDS) runs in one round after the carrier's tiles.
 // Deterministic mode: one workgroup per column block sums all S rows in a fixed order and
 // adds once (single writer).
-constexpr int kSlabColsPerBlock = 1024;
-// blocks of the gradient sum-of-squares pass: one fp32 partial each (elementwise.hip sumsq_kernel)
-constexpr int kSumsqBlocks = 512;
 // part: ≥ 4 KiB of 16-B aligned LDS.  Deterministic mode runs on the first 256 threads of the
 // carrier's workgroup (the others only join the barrier); the other mode splits the rows between
 // the two halves of a 512-thread carrier.  NV: row loads in flight per thread (a one-workgroup-
@@ -382,20 +367,7 @@ __device__ __forceinline__ void slab_reduce_block(const SlabJob& j, int b, float
   }
 }
 
-// fp32 gradient targets of the post-attention block (views of the flat gradient buffer).
-// Two sinks for a workgroup's parameter-gradient partials:
-//  * atomic (slab = 0): targets may be replicated: workgroup i adds into replica
-//    i % kGradReplicas, vrs floats apart (vrs = 0: one copy), folded once per step;
-//  * slab (slab = 1): workgroup i STORES its partials into row i of a (tiles, P) fp32 slab
-//    (vrs = P floats per row).  Float atomics execute at the memory side at ≈1.3 TB/s
-//    chip-wide, so 256 tiles × 50 KB of partials per kernel cost ≈10 µs of a ≈25 µs kernel;
-//    plain stores cost ≈0.3 µs per CU, and the slab rows are summed by a SlabJob.
-constexpr int kGradReplicas = 8;
-struct PostAttnGrads {
-  float *dWo, *dbo, *dg2, *dbe2, *dW1, *db1, *dW2, *db2;
-  int vrs;
-  int slab;
-};
+// a workgroup's slot of a PostAttnGrads target (host_api.h): its replica or its slab row
 __device__ __forceinline__ float* rep(float* p, int vrs, int slab) {
   return p + (long long)(slab ? blockIdx.x : (blockIdx.x & (kGradReplicas - 1))) * vrs;
 }
@@ -464,18 +436,7 @@ __device__ __forceinline__ bool keep_elem_m(uint32_t hs, uint32_t cm, uint32_t t
   return hash3_mix(hs ^ cm) >= thresh;
 }
 
-// Dropout configuration of one fused call.  The 64-bit seed lives in DEVICE memory: it is
-// drawn per forward call by torch's graph-safe generator (a 1-element randint on the step's
-// stream), so a replayed hipGraph reads a fresh seed every step instead of a value frozen at
-// capture time, and the backward regenerates the forward's masks from the same tensor.
-// ``site`` separates the masks of one call: sub-stream 0 = residual after attention,
-// 1 = residual after the MLP, 2 = attention probabilities (reference model.py:47-56, 66-71).
-struct DropCfg {
-  const int64_t* seed;  // nullptr or thresh == 0: dropout off
-  uint32_t site;
-  uint32_t thresh;      // p · 2^32
-  float scale;          // 1 / (1 - p)
-};
+// DropCfg (host_api.h): the per-call dropout configuration, its 64-bit seed in device memory
 __device__ __forceinline__ uint32_t drop_key(const int64_t* seed, uint32_t site, uint32_t sub) {
   const uint64_t s = (uint64_t)*seed;
   return hash3((uint32_t)s, (uint32_t)(s >> 32), site * 4u + sub);

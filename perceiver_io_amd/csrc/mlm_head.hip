@@ -666,8 +666,6 @@ static int pick_split(int M, int nchunks, int target) {
   return (nchunks + cps - 1) / cps;
 }
 
-int ce_combine_blocks(int M);
-
 // workgroup targets of the three CE launches (the C = 32 / 128 heads; C = 64 runs ce_head.hip)
 static int ce_target(const char*, int dflt) { return dflt; }
 

@@ -453,10 +453,6 @@ __global__ __launch_bounds__(256) void pe_grad_reduce_kernel(const float* __rest
   }
 }
 
-struct PeGradTargets {
-  float *dWa, *dWb, *db, *dg, *dbeta;  // dW rows [0, Ch) / [Ch, O) (kin columns each); any may be null
-};
-
 // one block per input column k (< kin), threads over the outputs o
 __global__ __launch_bounds__(256) void pe_grad_finalize_kernel(const float* __restrict__ Graw, const float* __restrict__ tot,
                                                                const float* __restrict__ Wa, const float* __restrict__ Wb,

@@ -1,7 +1,6 @@
 // Argument blocks of the persistent self-attention block kernels (persist.hip), shared by the
-// kernel translation unit and the host binding (binding.cpp) so the two cannot drift.  Include
-// after DropCfg / PostAttnGrads / SlabJob are declared (common.h on the device side, the mirrors
-// at the top of binding.cpp on the host side).
+// kernel translation unit and the host binding (binding.cpp) so the two cannot drift.  Included
+// by host_api.h after DropCfg is declared; include that header, not this one.
 #pragma once
 #include <stdint.h>
 

@@ -185,17 +185,7 @@ __device__ __forceinline__ void row_load(float (&v)[NCH][8], const T* __restrict
   }
 }
 
-// Fourier-PE split input (SURVEY K-03): logical row r = pe[r mod M] (row stride pe_rs, a
-// multiple of 8, with npix leading zero columns and zero padding past Kin) + the npix pixel
-// values of row r in those leading columns.  The (B, M, npix + C_pe) concatenation is never
-// materialised; the PE table stays L2/MALL-resident across the batch.  With idx given (sparse
-// images: the LArTPC events' non-zero pixels, models/lartpc.py) row r reads pe[idx[r]] instead
-// (clamped into the table), so the gathered [pixel ‖ PE] rows are not materialised either.
-struct PeSplit {
-  const float* pe;
-  int pe_rs, M, npix;
-  const long long* idx;
-};
+// PeSplit (host_api.h): the Fourier-PE split input.
 // An index outside the table is clamped (no fault); the eager PyTorch path (index_select) raises
 // instead.  Checked builds flag it (kErrPeIndex: the launcher raises outside graph capture,
 // ops.check_device_errors() after replays); the sparse collator only produces in-range indices.
@@ -1407,22 +1397,6 @@ static void set_smem_once(const void* fn) {
 // host side of the AV template flag: every pointer 16-B aligned (nullptr allowed), every row
 // stride / width a multiple of 8 elements
 static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-// register-resident chain kernels (CL layout, chain.hip) for the C = 64, H = 4 shapes; the LDS row-pass kernels otherwise
-bool sa_layer_fwd_chain_launch(const uint16_t* QKV, int N, float scale_log2, uint16_t* O, float* LSE, const float* X,
-                               const uint16_t* Wo, const float* bo, const float* g2, const float* be2, float eps,
-                               const uint16_t* W1, const float* b1, const uint16_t* W2, const float* b2, float* Z,
-                               float* Ysave, float* mean2, float* rstd2, uint16_t* Usave, int R, const float* lnw,
-                               const float* lnb, const uint16_t* Wq, const float* bq, uint16_t* QKVn, float* mean1,
-                               float* rstd1, const DropCfg& dr, int nq, hipStream_t st);
-bool ln_linear_post_attn_bwd_chain_launch(const void* G, bool g_bf16, const uint16_t* Wq, const float* X, const float* mean1,
-                                          const float* rstd1, const float* lnw, const float* lnb, const float* dres,
-                                          float* dlnw, float* dlnb, float* dWq, float* dbq, const float* Ysave,
-                                          const float* mean2, const float* rstd2, const uint16_t* U, const uint16_t* O,
-                                          const uint16_t* Wo, const uint16_t* W1, const uint16_t* W2, const float* g2,
-                                          const float* be2, float* dY, uint16_t* dO, float* delta,
-                                          const PostAttnGrads& grads, int R, const SlabJob& job, const DropCfg& dr,
-                                          int nq, const uint16_t* att_qkv, const float* att_lse, uint16_t* att_out,
-                                          float att_scale, hipStream_t st);
 static bool av_ok(std::initializer_list<const void*> ptrs, std::initializer_list<long long> widths) {
   for (const void* p : ptrs)
     if (!al16(p)) return false;
@@ -1448,264 +1422,206 @@ static int pick_nch(int K) {
 }
 
 template <typename TI, typename TO, int NCH>
-static void ln_linear_fwd_t(const void* X, int x_rs, int R, int Kin, const float* lnw, const float* lnb, float eps,
-                            const uint16_t* W, int w_rs, const float* bias, int N, int act, const float* res, int res_rs,
-                            void* Y, int y_rs, float* mean, float* rstd, const PeSplit& ps, hipStream_t st) {
-  constexpr int KP = 32 * NCH;
+static void ln_linear_fwd_t(const LnLinearFwdArgs& a, hipStream_t st) {
   const size_t smem = ln_linear_fwd_smem<NCH>();
-  const bool av = av_ok({X, W, lnw, lnb}, {Kin, x_rs, w_rs});
-  const int vf = av ? 0 : vec_flags(nullptr, 0, 0, W, w_rs, Kin, lnw, lnb);
+  const bool av = av_ok({a.X.p, a.W, a.lnw, a.lnb}, {a.Kin, a.X.rs, a.w_rs});
+  const int vf = av ? 0 : vec_flags(nullptr, 0, 0, a.W, a.w_rs, a.Kin, a.lnw, a.lnb);
   auto fn = av ? ln_linear_fwd_kernel<TI, TO, NCH, true> : ln_linear_fwd_kernel<TI, TO, NCH, false>;
   set_smem_once((const void*)fn);
   // few tiles: several workgroups per tile, each forming every split_tiles(R)-th 64-column chunk
-  hipLaunchKernelGGL(fn, dim3((R + 63) / 64, split_tiles(R)), dim3(256), smem, st, (const TI*)X, x_rs, R, Kin, lnw, lnb,
-                     eps, W, w_rs, bias, N, act, res, res_rs, (TO*)Y, y_rs, mean, rstd, ps, vf);
+  hipLaunchKernelGGL(fn, dim3((a.R + 63) / 64, split_tiles(a.R)), dim3(256), smem, st, (const TI*)a.X.p, a.X.rs, a.R,
+                     a.Kin, a.lnw, a.lnb, a.eps, a.W, a.w_rs, a.bias, a.N, a.act, a.res, a.res_rs, (TO*)a.Y.p, a.Y.rs,
+                     a.mean, a.rstd, a.ps, vf);
 }
 
 template <typename TI, typename TO>
-static void ln_linear_fwd_n(int nch, const void* X, int x_rs, int R, int Kin, const float* lnw, const float* lnb,
-                            float eps, const uint16_t* W, int w_rs, const float* bias, int N, int act, const float* res,
-                            int res_rs, void* Y, int y_rs, float* mean, float* rstd, const PeSplit& ps,
-                            hipStream_t st) {
-#define LNF(K) \
-  ln_linear_fwd_t<TI, TO, K>(X, x_rs, R, Kin, lnw, lnb, eps, W, w_rs, bias, N, act, res, res_rs, Y, y_rs, mean, rstd, ps, st)
+static void ln_linear_fwd_n(int nch, const LnLinearFwdArgs& a, hipStream_t st) {
   switch (nch) {
-    case 1: LNF(1); break;
-    case 2: LNF(2); break;
-    case 4: LNF(4); break;
-    case 5: LNF(5); break;
-    default: LNF(8); break;
+    case 1: ln_linear_fwd_t<TI, TO, 1>(a, st); break;
+    case 2: ln_linear_fwd_t<TI, TO, 2>(a, st); break;
+    case 4: ln_linear_fwd_t<TI, TO, 4>(a, st); break;
+    case 5: ln_linear_fwd_t<TI, TO, 5>(a, st); break;
+    default: ln_linear_fwd_t<TI, TO, 8>(a, st); break;
   }
-#undef LNF
 }
 
-void ln_linear_fwd_launch(const void* X, bool x_bf16, int x_rs, int R, int Kin, const float* lnw, const float* lnb,
-                          float eps, const uint16_t* W, int w_rs, const float* bias, int N, int act, const float* res,
-                          int res_rs, void* Y, bool y_bf16, int y_rs, float* mean, float* rstd, const float* pe, int pe_rs,
-                          int pe_rows, int npix, const long long* pe_idx, hipStream_t st) {
-  const int nch = pick_nch(Kin);
-  const PeSplit ps{pe, pe_rs, pe_rows, npix, pe_idx};
-#define LNL(TI, TO) \
-  ln_linear_fwd_n<TI, TO>(nch, X, x_rs, R, Kin, lnw, lnb, eps, W, w_rs, bias, N, act, res, res_rs, Y, y_rs, mean, rstd, ps, st)
-  if (x_bf16 && y_bf16) LNL(uint16_t, uint16_t);
-  else if (x_bf16) LNL(uint16_t, float);
-  else if (y_bf16) LNL(float, uint16_t);
-  else LNL(float, float);
-#undef LNL
+void ln_linear_fwd_launch(const LnLinearFwdArgs& a, hipStream_t st) {
+  const int nch = pick_nch(a.Kin);
+  if (a.X.bf16 && a.Y.bf16) ln_linear_fwd_n<uint16_t, uint16_t>(nch, a, st);
+  else if (a.X.bf16) ln_linear_fwd_n<uint16_t, float>(nch, a, st);
+  else if (a.Y.bf16) ln_linear_fwd_n<float, uint16_t>(nch, a, st);
+  else ln_linear_fwd_n<float, float>(nch, a, st);
 }
 
-void post_attn_fwd_launch(int C, const uint16_t* O, const float* X, const uint16_t* Wo, const float* bo,
-                          const float* g2, const float* be2, float eps, const uint16_t* W1, const float* b1,
-                          const uint16_t* W2, const float* b2, float* Z, float* Ysave, float* mean2, float* rstd2,
-                          uint16_t* Usave, int R, int Rx, const DropCfg& dr, hipStream_t st) {
-  const bool av = av_ok({O, X, Wo, W1, W2, Z, Ysave, Usave}, {});
-  dim3 grid((R + 63) / 64);
-#define PAF(CC)                                                                                                     \
-  if (av) hipLaunchKernelGGL((post_attn_fwd_kernel<CC, true>), grid, dim3(256), 0, st, O, X, Wo, bo, g2, be2, eps, \
-                             W1, b1, W2, b2, Z, Ysave, mean2, rstd2, Usave, R, Rx, dr);                         \
-  else hipLaunchKernelGGL((post_attn_fwd_kernel<CC, false>), grid, dim3(256), 0, st, O, X, Wo, bo, g2, be2, eps,   \
-                          W1, b1, W2, b2, Z, Ysave, mean2, rstd2, Usave, R, Rx, dr)
-  if (C == 64) PAF(64);
-  else if (C == 128) PAF(128);
-  else if (C == 32) PAF(32);
+void post_attn_fwd_launch(const PostAttnFwdArgs& a, int C, hipStream_t st) {
+  const PostAttnParams& p = a.p;
+  const PostAttnSaved& s = a.s;
+  const bool av = av_ok({a.O, a.X, p.Wo, p.W1, p.W2, a.Z, s.Ysave, s.Usave}, {});
+  dim3 grid((a.R + 63) / 64);
+#define PAF(CC)                                                                                              \
+  {                                                                                                          \
+    auto fn = av ? post_attn_fwd_kernel<CC, true> : post_attn_fwd_kernel<CC, false>;                         \
+    hipLaunchKernelGGL(fn, grid, dim3(256), 0, st, a.O, a.X, p.Wo, p.bo, p.g2, p.be2, p.eps, p.W1, p.b1, p.W2, \
+                       p.b2, a.Z, s.Ysave, s.mean2, s.rstd2, s.Usave, a.R, a.Rx, a.dr);                      \
+  }
+  if (C == 64) PAF(64)
+  else if (C == 128) PAF(128)
+  else if (C == 32) PAF(32)
 #undef PAF
 }
 
-void post_attn_ln_linear_fwd_launch(int C, const uint16_t* O, const float* X, const uint16_t* Wo, const float* bo,
-                                    const float* g2, const float* be2, float eps, const uint16_t* W1, const float* b1,
-                                    const uint16_t* W2, const float* b2, float* Z, float* Ysave, float* mean2,
-                                    float* rstd2, uint16_t* Usave, int R, int Rx, const float* lnw, const float* lnb,
-                                    const uint16_t* Wq, const float* bq, uint16_t* QKV, float* mean1, float* rstd1,
-                                    const DropCfg& dr, hipStream_t st) {
-  const bool av = av_ok({O, X, Wo, W1, W2, Z, Ysave, Usave, Wq, lnw, lnb, QKV}, {});
-  dim3 grid((R + 63) / 64, split_tiles(R));
-#define PLF(CC)                                                                                                  \
-  if (av) hipLaunchKernelGGL((post_attn_ln_linear_fwd_kernel<CC, true>), grid, dim3(256), 0, st, O, X, Wo, bo, g2, \
-                             be2, eps, W1, b1, W2, b2, Z, Ysave, mean2, rstd2, Usave, R, Rx, lnw, lnb, Wq, bq, QKV,  \
-                             mean1, rstd1, dr);                                                                    \
-  else hipLaunchKernelGGL((post_attn_ln_linear_fwd_kernel<CC, false>), grid, dim3(256), 0, st, O, X, Wo, bo, g2,     \
-                          be2, eps, W1, b1, W2, b2, Z, Ysave, mean2, rstd2, Usave, R, Rx, lnw, lnb, Wq, bq, QKV,     \
-                          mean1, rstd1, dr)
-  if (C == 64) PLF(64);
-  else if (C == 128) PLF(128);
-  else if (C == 32) PLF(32);
+void post_attn_ln_linear_fwd_launch(const PostAttnFwdArgs& a, int C, hipStream_t st) {
+  const PostAttnParams& p = a.p;
+  const PostAttnSaved& s = a.s;
+  const NextProj& n = a.next;
+  const bool av = av_ok({a.O, a.X, p.Wo, p.W1, p.W2, a.Z, s.Ysave, s.Usave, n.Wq, n.lnw, n.lnb, n.QKVn}, {});
+  dim3 grid((a.R + 63) / 64, split_tiles(a.R));
+#define PLF(CC)                                                                                                \
+  {                                                                                                            \
+    auto fn = av ? post_attn_ln_linear_fwd_kernel<CC, true> : post_attn_ln_linear_fwd_kernel<CC, false>;       \
+    hipLaunchKernelGGL(fn, grid, dim3(256), 0, st, a.O, a.X, p.Wo, p.bo, p.g2, p.be2, p.eps, p.W1, p.b1, p.W2,   \
+                       p.b2, a.Z, s.Ysave, s.mean2, s.rstd2, s.Usave, a.R, a.Rx, n.lnw, n.lnb, n.Wq, n.bq, n.QKVn, \
+                       n.mean1, n.rstd1, a.dr);                                                                \
+  }
+  if (C == 64) PLF(64)
+  else if (C == 128) PLF(128)
+  else if (C == 32) PLF(32)
 #undef PLF
 }
 
 // fused self-attention layer forward (C = 64, H = 4): the chain kernel (chain.hip
 // sa_layer_fwd_chain8_kernel); false (nothing launched) when the operands do not qualify (every
 // pointer 16-byte aligned, N <= 512) — the binding turns that into an error
-bool sa_layer_fwd_launch(const uint16_t* QKV, int N, float scale_log2, uint16_t* O, float* LSE, const float* X,
-                         const uint16_t* Wo, const float* bo, const float* g2, const float* be2, float eps,
-                         const uint16_t* W1, const float* b1, const uint16_t* W2, const float* b2, float* Z,
-                         float* Ysave, float* mean2, float* rstd2, uint16_t* Usave, int R, const float* lnw,
-                         const float* lnb, const uint16_t* Wq, const float* bq, uint16_t* QKVn, float* mean1,
-                         float* rstd1, const DropCfg& dr, int nq, hipStream_t st) {
-  const bool av = av_ok({QKV, O, X, Wo, W1, W2, Z, Ysave, Usave, Wq, lnw, lnb, QKVn}, {});
-  return av && sa_layer_fwd_chain_launch(QKV, N, scale_log2, O, LSE, X, Wo, bo, g2, be2, eps, W1, b1, W2, b2, Z, Ysave,
-                                         mean2, rstd2, Usave, R, lnw, lnb, Wq, bq, QKVn, mean1, rstd1, dr, nq, st);
+bool sa_layer_fwd_launch(const SaLayerFwdArgs& a, hipStream_t st) {
+  const bool av = av_ok({a.QKV, a.O, a.X, a.p.Wo, a.p.W1, a.p.W2, a.Z, a.s.Ysave, a.s.Usave, a.next.Wq, a.next.lnw,
+                         a.next.lnb, a.next.QKVn},
+                        {});
+  return av && sa_layer_fwd_chain_launch(a, st);
 }
 
-void post_attn_bwd_launch(int C, const float* dZ, const float* Ysave, const float* mean2, const float* rstd2,
-                          const uint16_t* U, const uint16_t* O, const uint16_t* Wo, const uint16_t* W1,
-                          const uint16_t* W2, const float* g2, const float* be2, float* dY, uint16_t* dO,
-                          float* delta, int H, const PostAttnGrads& grads, int R, const SlabJob& job, const DropCfg& dr,
-                          hipStream_t st) {
-  const int spl = split_tiles(R);
-  dim3 grid((R + 63) / 64 + (job.slab ? (job.nblk + spl - 1) / spl : 0), spl);
-  const bool av = av_ok({dZ, Ysave, U, O, Wo, W1, W2, dY, dO}, {});
-#define PAB(CC)                                                                                                  \
-  if (av) hipLaunchKernelGGL((post_attn_bwd_kernel<CC, true>), grid, dim3(256), 0, st, dZ, Ysave, mean2, rstd2, U, \
-                             O, Wo, W1, W2, g2, be2, dY, dO, delta, H, grads, R, job, dr);                        \
-  else hipLaunchKernelGGL((post_attn_bwd_kernel<CC, false>), grid, dim3(256), 0, st, dZ, Ysave, mean2, rstd2, U, O,  \
-                          Wo, W1, W2, g2, be2, dY, dO, delta, H, grads, R, job, dr)
-  if (C == 64) PAB(64);
-  else if (C == 128) PAB(128);
-  else if (C == 32) PAB(32);
+void post_attn_bwd_launch(const PostAttnBwdArgs& a, int C, hipStream_t st) {
+  const PostAttnParams& p = a.p;
+  const PostAttnSaved& s = a.s;
+  const int spl = split_tiles(a.R);
+  dim3 grid((a.R + 63) / 64 + (a.job.slab ? (a.job.nblk + spl - 1) / spl : 0), spl);
+  const bool av = av_ok({a.dZ, s.Ysave, s.Usave, a.O, p.Wo, p.W1, p.W2, a.dY, a.dO}, {});
+#define PAB(CC)                                                                                                \
+  {                                                                                                            \
+    auto fn = av ? post_attn_bwd_kernel<CC, true> : post_attn_bwd_kernel<CC, false>;                           \
+    hipLaunchKernelGGL(fn, grid, dim3(256), 0, st, a.dZ, s.Ysave, s.mean2, s.rstd2, s.Usave, a.O, p.Wo, p.W1,    \
+                       p.W2, p.g2, p.be2, a.dY, a.dO, a.delta, a.H, a.grads, a.R, a.job, a.dr);                \
+  }
+  if (C == 64) PAB(64)
+  else if (C == 128) PAB(128)
+  else if (C == 32) PAB(32)
 #undef PAB
 }
 
 // G: fp32, or (g_bf16) bf16 — taken by the chain-layout kernel only; returns false (nothing
 // launched) for a bf16 G the chain kernel cannot take (the caller converts it to fp32)
-bool ln_linear_post_attn_bwd_launch(int C, const void* Gv, bool g_bf16, const uint16_t* Wq, const float* X, const float* mean1,
-                                    const float* rstd1, const float* lnw, const float* lnb, const float* dres,
-                                    float* dlnw, float* dlnb, float* dWq, float* dbq, const float* Ysave,
-                                    const float* mean2, const float* rstd2, const uint16_t* U, const uint16_t* O,
-                                    const uint16_t* Wo, const uint16_t* W1, const uint16_t* W2, const float* g2,
-                                    const float* be2, float* dY, uint16_t* dO, float* delta, int H,
-                                    const PostAttnGrads& grads, int R, const SlabJob& job, const DropCfg& dr,
-                                    int nq, const uint16_t* att_qkv, const float* att_lse, uint16_t* att_out,
-                                    float att_scale, hipStream_t st) {
-  dim3 grid((R + 63) / 64 + (job.slab ? job.nblk : 0));
-  const float* G = static_cast<const float*>(Gv);
-  const bool av = av_ok({Gv, Wq, X, lnw, lnb, dres, Ysave, U, O, Wo, W1, W2, dY, dO}, {});
-  const bool att = att_out != nullptr;  // the fused attention backward (chain kernel only)
-  if (att && !(av && al16(att_qkv) && al16(att_out) && al16(att_lse))) return false;
-  if (av && C == 64 && H == 4 && grads.slab && (R % 64) == 0 &&
-      ln_linear_post_attn_bwd_chain_launch(Gv, g_bf16, Wq, X, mean1, rstd1, lnw, lnb, dres, dlnw, dlnb, dWq, dbq, Ysave,
-                                           mean2, rstd2, U, O, Wo, W1, W2, g2, be2, dY, dO, delta, grads, R, job, dr, nq,
-                                           att_qkv, att_lse, att_out, att_scale, st))
+bool ln_linear_post_attn_bwd_launch(const LnLinearPostAttnBwdArgs& a, int C, hipStream_t st) {
+  const PostAttnBwdArgs& b = a.pa;
+  const PostAttnParams& p = b.p;
+  const PostAttnSaved& s = b.s;
+  const NextProj& n = a.next;
+  const int R = b.R;
+  dim3 grid((R + 63) / 64 + (b.job.slab ? b.job.nblk : 0));
+  const float* G = static_cast<const float*>(a.G);
+  const bool av = av_ok({a.G, n.Wq, a.X, n.lnw, n.lnb, a.dres, s.Ysave, s.Usave, b.O, p.Wo, p.W1, p.W2, b.dY, b.dO}, {});
+  const bool att = a.att.out != nullptr;  // the fused attention backward (chain kernel only)
+  if (att && !(av && al16(a.att.qkv) && al16(a.att.out) && al16(a.att.lse))) return false;
+  // register-resident chain kernel (CL layout, chain.hip) for the C = 64, H = 4 shapes; the LDS row-pass kernels otherwise
+  if (av && C == 64 && b.H == 4 && b.grads.slab && (R % 64) == 0 && ln_linear_post_attn_bwd_chain_launch(a, st))
     return true;
-  if (g_bf16 || att) return false;
+  if (a.g_bf16 || att) return false;
   grid.y = split_tiles(R);
-  grid.x = (R + 63) / 64 + (job.slab ? (job.nblk + (int)grid.y - 1) / (int)grid.y : 0);
+  grid.x = (R + 63) / 64 + (b.job.slab ? (b.job.nblk + (int)grid.y - 1) / (int)grid.y : 0);
 #define LPB(CC, NQ)                                                                                               \
-  if (av) hipLaunchKernelGGL((ln_linear_post_attn_bwd_kernel<CC, true, NQ>), grid, dim3(256), 0, st, G, Wq, X, mean1, \
-                             rstd1, lnw, lnb, dres, dlnw, dlnb, dWq, dbq, Ysave, mean2, rstd2, U, O, Wo, W1, W2, g2, \
-                             be2, dY, dO, delta, H, grads, R, job, dr);                                            \
-  else hipLaunchKernelGGL((ln_linear_post_attn_bwd_kernel<CC, false, NQ>), grid, dim3(256), 0, st, G, Wq, X, mean1,  \
-                          rstd1, lnw, lnb, dres, dlnw, dlnb, dWq, dbq, Ysave, mean2, rstd2, U, O, Wo, W1, W2, g2,    \
-                          be2, dY, dO, delta, H, grads, R, job, dr)
-  if (C == 64 && nq == 3 * C) { LPB(64, 3); }
-  else if (C == 64) { LPB(64, 1); }
-  else if (C == 128 && nq == 3 * C) { LPB(128, 3); }
-  else if (C == 128) { LPB(128, 1); }
-  else if (nq == 3 * C) { LPB(32, 3); }
-  else { LPB(32, 1); }
+  {                                                                                                               \
+    auto fn = av ? ln_linear_post_attn_bwd_kernel<CC, true, NQ> : ln_linear_post_attn_bwd_kernel<CC, false, NQ>;  \
+    hipLaunchKernelGGL(fn, grid, dim3(256), 0, st, G, n.Wq, a.X, n.mean1, n.rstd1, n.lnw, n.lnb, a.dres, a.dlnw,    \
+                       a.dlnb, a.dWq, a.dbq, s.Ysave, s.mean2, s.rstd2, s.Usave, b.O, p.Wo, p.W1, p.W2, p.g2, p.be2, \
+                       b.dY, b.dO, b.delta, b.H, b.grads, R, b.job, b.dr);                                        \
+  }
+  if (C == 64 && n.nq == 3 * C) LPB(64, 3)
+  else if (C == 64) LPB(64, 1)
+  else if (C == 128 && n.nq == 3 * C) LPB(128, 3)
+  else if (C == 128) LPB(128, 1)
+  else if (n.nq == 3 * C) LPB(32, 3)
+  else LPB(32, 1)
 #undef LPB
   return true;
 }
 
 template <typename TG, typename TX, int NCH>
-static void ln_linear_bwd_t(const void* G, int g_rs, int N, const uint16_t* W, int w_rs, int Kin, const void* X, int x_rs,
-                            const float* mean, const float* rstd, const float* lnw, const float* lnb, const float* dres,
-                            int dres_rs, float* dX, int dx_rs, float* dlnw, float* dlnb, float* dW, float* db, int vrs,
-                            int wrs, int slab, int R, const PeSplit& ps, const SlabJob& job, hipStream_t st) {
-  constexpr int KP = 32 * NCH;
+static void ln_linear_bwd_t(const LnLinearBwdArgs& a, hipStream_t st) {
   const size_t smem = ln_linear_bwd_smem<NCH>();
-  const bool av = av_ok({G, W, X, lnw, lnb, dres}, {N, g_rs, w_rs, Kin, x_rs, dres ? dres_rs : 0});
-  const int vf = av ? 0 : vec_flags(G, g_rs, N, W, w_rs, Kin, lnw, lnb);
+  const bool av = av_ok({a.G.p, a.W, a.X.p, a.lnw, a.lnb, a.dres},
+                        {a.N, a.G.rs, a.w_rs, a.Kin, a.X.rs, a.dres ? a.dres_rs : 0});
+  const int vf = av ? 0 : vec_flags(a.G.p, a.G.rs, a.N, a.W, a.w_rs, a.Kin, a.lnw, a.lnb);
   auto fn = av ? ln_linear_bwd_kernel<TG, TX, NCH, true> : ln_linear_bwd_kernel<TG, TX, NCH, false>;
   set_smem_once((const void*)fn);
   // + the appended slab-job workgroups; few tiles: several workgroups per tile (split_tiles)
-  const int spl = split_tiles(R);
-  const dim3 grid((R + 63) / 64 + (job.slab ? (job.nblk + spl - 1) / spl : 0), spl);
-  hipLaunchKernelGGL(fn, grid, dim3(256), smem, st, (const TG*)G, g_rs, N, W, w_rs, Kin, (const TX*)X, x_rs,
-                     mean, rstd, lnw, lnb, dres, dres_rs, dX, dx_rs, dlnw, dlnb, dW, db, vrs, wrs, slab, R, ps, job, vf);
+  const int spl = split_tiles(a.R);
+  const dim3 grid((a.R + 63) / 64 + (a.job.slab ? (a.job.nblk + spl - 1) / spl : 0), spl);
+  hipLaunchKernelGGL(fn, grid, dim3(256), smem, st, (const TG*)a.G.p, a.G.rs, a.N, a.W, a.w_rs, a.Kin, (const TX*)a.X.p,
+                     a.X.rs, a.mean, a.rstd, a.lnw, a.lnb, a.dres, a.dres_rs, a.dX, a.dx_rs, a.dlnw, a.dlnb, a.dW, a.db,
+                     a.vrs, a.wrs, a.slab, a.R, a.ps, a.job, vf);
 }
 
 template <typename TG, typename TX>
-static void ln_linear_bwd_n(int nch, const void* G, int g_rs, int N, const uint16_t* W, int w_rs, int Kin, const void* X,
-                            int x_rs, const float* mean, const float* rstd, const float* lnw, const float* lnb,
-                            const float* dres, int dres_rs, float* dX, int dx_rs, float* dlnw, float* dlnb, float* dW,
-                            float* db, int vrs, int wrs, int slab, int R, const PeSplit& ps, const SlabJob& job,
-                            hipStream_t st) {
-#define LNB(K)                                                                                                    \
-  ln_linear_bwd_t<TG, TX, K>(G, g_rs, N, W, w_rs, Kin, X, x_rs, mean, rstd, lnw, lnb, dres, dres_rs, dX, dx_rs, dlnw, \
-                             dlnb, dW, db, vrs, wrs, slab, R, ps, job, st)
+static void ln_linear_bwd_n(int nch, const LnLinearBwdArgs& a, hipStream_t st) {
   switch (nch) {
-    case 1: LNB(1); break;
-    case 2: LNB(2); break;
-    case 4: LNB(4); break;
-    default: LNB(5); break;
+    case 1: ln_linear_bwd_t<TG, TX, 1>(a, st); break;
+    case 2: ln_linear_bwd_t<TG, TX, 2>(a, st); break;
+    case 4: ln_linear_bwd_t<TG, TX, 4>(a, st); break;
+    default: ln_linear_bwd_t<TG, TX, 5>(a, st); break;
   }
-#undef LNB
 }
 
-void ln_linear_bwd_launch(const void* G, bool g_bf16, int g_rs, int N, const uint16_t* W, int w_rs, int Kin, const void* X,
-                          bool x_bf16, int x_rs, const float* mean, const float* rstd, const float* lnw,
-                          const float* lnb, const float* dres, int dres_rs, float* dX, int dx_rs, float* dlnw,
-                          float* dlnb, float* dW, float* db, int vrs, int wrs, int slab, int R, const float* pe,
-                          int pe_rs, int pe_rows, int npix, const long long* pe_idx, const SlabJob& job, hipStream_t st) {
-  const int nch = pick_nch(Kin);  // Kin ≤ 160 → ≤ 5
-  const PeSplit ps{pe, pe_rs, pe_rows, npix, pe_idx};
-#define LDG(TG, TX)                                                                                           \
-  ln_linear_bwd_n<TG, TX>(nch, G, g_rs, N, W, w_rs, Kin, X, x_rs, mean, rstd, lnw, lnb, dres, dres_rs, dX, dx_rs, \
-                          dlnw, dlnb, dW, db, vrs, wrs, slab, R, ps, job, st)
-  if (g_bf16 && x_bf16) LDG(uint16_t, uint16_t);
-  else if (g_bf16) LDG(uint16_t, float);
-  else if (x_bf16) LDG(float, uint16_t);
-  else LDG(float, float);
-#undef LDG
+void ln_linear_bwd_launch(const LnLinearBwdArgs& a, hipStream_t st) {
+  const int nch = pick_nch(a.Kin);  // Kin ≤ 160 → ≤ 5
+  if (a.G.bf16 && a.X.bf16) ln_linear_bwd_n<uint16_t, uint16_t>(nch, a, st);
+  else if (a.G.bf16) ln_linear_bwd_n<uint16_t, float>(nch, a, st);
+  else if (a.X.bf16) ln_linear_bwd_n<float, uint16_t>(nch, a, st);
+  else ln_linear_bwd_n<float, float>(nch, a, st);
 }
 
 template <typename TG, typename TA, int NCH>
-static void wgrad_t(const void* G, int g_rs, int N, const void* A, int a_rs, int Kin, int amode, const float* mean,
-                    const float* rstd, const float* lnw, const float* lnb, int R, int rps, float* dW, float* db,
-                    int vrs, int wrs, const PeSplit& ps, hipStream_t st) {
+static void wgrad_t(const WgradArgs& a, int rps, hipStream_t st) {
   constexpr int KP = 32 * NCH;
   const size_t smem = (64 * (64 + 8) + 64 * (KP + 8)) * 2 + 2 * KP * 4 + 4 * 64 * 4;
   auto fn = wgrad_kernel<TG, TA, NCH>;
   set_smem_once((const void*)fn);
-  dim3 grid((N + 63) / 64, (R + rps - 1) / rps);
-  hipLaunchKernelGGL(fn, grid, dim3(256), smem, st, (const TG*)G, g_rs, N, (const TA*)A, a_rs, Kin, amode, mean, rstd,
-                     lnw, lnb, R, rps, dW, db, vrs, wrs, ps);
+  dim3 grid((a.N + 63) / 64, (a.R + rps - 1) / rps);
+  hipLaunchKernelGGL(fn, grid, dim3(256), smem, st, (const TG*)a.G.p, a.G.rs, a.N, (const TA*)a.A.p, a.A.rs, a.Kin,
+                     a.amode, a.mean, a.rstd, a.lnw, a.lnb, a.R, rps, a.dW, a.db, a.vrs, a.wrs, a.ps);
 }
 
 template <typename TG, typename TA>
-static void wgrad_n(int nch, const void* G, int g_rs, int N, const void* A, int a_rs, int Kin, int amode,
-                    const float* mean, const float* rstd, const float* lnw, const float* lnb, int R, int rps, float* dW,
-                    float* db, int vrs, int wrs, const PeSplit& ps, hipStream_t st) {
-#define WGN(K) wgrad_t<TG, TA, K>(G, g_rs, N, A, a_rs, Kin, amode, mean, rstd, lnw, lnb, R, rps, dW, db, vrs, wrs, ps, st)
+static void wgrad_n(int nch, const WgradArgs& a, int rps, hipStream_t st) {
   switch (nch) {
-    case 1: WGN(1); break;
-    case 2: WGN(2); break;
-    case 4: WGN(4); break;
-    default: WGN(5); break;
+    case 1: wgrad_t<TG, TA, 1>(a, rps, st); break;
+    case 2: wgrad_t<TG, TA, 2>(a, rps, st); break;
+    case 4: wgrad_t<TG, TA, 4>(a, rps, st); break;
+    default: wgrad_t<TG, TA, 5>(a, rps, st); break;
   }
-#undef WGN
 }
 
 // rows_per_wg ≤ 0: pick the split so that the launch has ≈ 512 workgroups
-void wgrad_launch(const void* G, bool g_bf16, int g_rs, int N, const void* A, bool a_bf16, int a_rs, int Kin,
-                  int amode, const float* mean, const float* rstd, const float* lnw, const float* lnb, int R,
-                  int rows_per_wg, float* dW, float* db, int vrs, int wrs, const float* pe, int pe_rs, int pe_rows,
-                  int npix, const long long* pe_idx, hipStream_t st) {
-  const int nblk = (N + 63) / 64;
-  int rps = rows_per_wg;
+void wgrad_launch(const WgradArgs& a, hipStream_t st) {
+  const int nblk = (a.N + 63) / 64;
+  int rps = a.rows_per_wg;
   if (rps <= 0) {
     const int splits = (512 + nblk - 1) / nblk;
-    rps = (R + splits - 1) / splits;
+    rps = (a.R + splits - 1) / splits;
   }
   rps = round_up(rps < 64 ? 64 : rps, 64);
-  const PeSplit ps{pe, pe_rs, pe_rows, npix, pe_idx};
-  const int nch = pick_nch(Kin);
-#define WG(TG, TA) wgrad_n<TG, TA>(nch, G, g_rs, N, A, a_rs, Kin, amode, mean, rstd, lnw, lnb, R, rps, dW, db, vrs, wrs, ps, st)
-  if (g_bf16 && a_bf16) WG(uint16_t, uint16_t);
-  else if (g_bf16) WG(uint16_t, float);
-  else if (a_bf16) WG(float, uint16_t);
-  else WG(float, float);
-#undef WG
+  const int nch = pick_nch(a.Kin);
+  if (a.G.bf16 && a.A.bf16) wgrad_n<uint16_t, uint16_t>(nch, a, rps, st);
+  else if (a.G.bf16) wgrad_n<uint16_t, float>(nch, a, rps, st);
+  else if (a.A.bf16) wgrad_n<float, uint16_t>(nch, a, rps, st);
+  else wgrad_n<float, float>(nch, a, rps, st);
 }
 
 }  // namespace pio

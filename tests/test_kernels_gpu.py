@@ -139,6 +139,27 @@ def test_attention_fwd_bwd(B, Bq, Nq, Nk, H, D, ns):
         close(dkv[:, :, E:], 2 * g2[2], 3e-2, "dv accumulated")
 
 
+def test_attention_bwd_deterministic_key_blocks():
+    """Deterministic mode with several key blocks: each block stores its own dQ slice and the
+    slices are summed in a fixed order — same values as the atomic path's reference, and bit for
+    bit the same from run to run."""
+    from perceiver_io_amd import ops
+
+    torch.manual_seed(2)
+    B, Nq, Nk, H, D = 2, 64, 600, 4, 16
+    q, k, v, km = _attn_inputs(B, B, Nq, Nk, H, D)
+    scale = 1.0 / math.sqrt(D)
+    o, lse = _ext().attn_fwd(q, k, v, km, H, D, scale, 0.0, None, 1)
+    do = bf(torch.randn(B, Nq, H * D, device=DEV))
+    ref = _emu().attn_bwd(q, k, v, km, o, do, lse, None, H, D, scale, 0.0, None, None, None, None)
+    ops.set_deterministic(True)  # put back by the autouse fixture
+    runs = [_ext().attn_bwd(q, k, v, km, o, do, lse, None, H, D, scale, 0.0, None, None, None, None) for _ in range(2)]
+    for a, b, n in zip(runs[0], ref, ("dq", "dk", "dv")):
+        close(a, b, 3e-2, n)
+    for a, b in zip(*runs):
+        assert torch.equal(a, b)
+
+
 def _seed(v):
     return torch.tensor([v], dtype=torch.int64, device=DEV)
 
@@ -275,6 +296,24 @@ def test_post_attn(C, H):
                          job_dsts=[t.view(-1) for t in dst2], job_offs=offs)
     for i, n in enumerate(names):
         close(dst2[i], gb[3 + i], 3e-2, n + " (slab job)")
+
+
+def test_post_attn_ln_linear_fwd():
+    """The row-tile layer-boundary forward (post-attention block of layer l, then LN1 + packed QKV
+    projection of layer l+1) over two 64-row tiles."""
+    torch.manual_seed(5)
+    R, C = 128, 64
+    o = bf(torch.randn(R, C, device=DEV))
+    x = torch.randn(R, C, device=DEV)
+    ws = [bf(torch.randn(C, C, device=DEV) / math.sqrt(C)) for _ in range(3)]
+    bo, b1, b2 = (torch.randn(C, device=DEV) * 0.1 for _ in range(3))
+    g2, be2 = torch.randn(C, device=DEV), torch.randn(C, device=DEV)
+    lnw, lnb = torch.randn(C, device=DEV), torch.randn(C, device=DEV)
+    wq, bq = bf(torch.randn(3 * C, C, device=DEV) / math.sqrt(C)), torch.randn(3 * C, device=DEV) * 0.1
+    a, b = (K.post_attn_ln_linear_fwd(o, x, ws[0], bo, g2, be2, 1e-5, ws[1], b1, ws[2], b2, lnw, lnb, wq, bq)
+            for K in (_ext(), _emu()))
+    for t1, t2, n in zip(a, b, ("z", "y", "mean2", "rstd2", "u", "qkv", "mean1", "rstd1")):
+        close(t1, t2, 2e-2, n)
 
 
 @pytest.mark.parametrize("R,N,Kin,gbf", [(300, 192, 64, False), (200, 128, 131, False), (129, 64, 64, True)])
@@ -445,6 +484,59 @@ def test_split_pe_input_projection(R, M, npix, kin, tall):
         K.wgrad(g, pix, 1, mean, rstd, lw, lb, 0, dW2, db2, pe, kin)
         res.append((dg, dbn, dW, dbias, dW2, db2))
     for a, b, n in zip(res[0], res[1], ("dgamma", "dbeta", "dW", "dbias", "wgrad dW", "wgrad db")):
+        close(a, b, 3e-2, n)
+
+
+def test_split_pe_input_gathered_rows():
+    """The split input with a row index (pe_index: row r reads pe[pe_index[r]], the sparse images'
+    gathered rows) through the forward, the backward and the standalone weight gradient, at an odd
+    input width (131) over two 64-row tiles."""
+    torch.manual_seed(19)
+    R, M, npix, kin, N = 128, 50, 1, 131, 64
+    pe = torch.zeros(M, (kin + 7) // 8 * 8, device=DEV)
+    pe[:, npix:kin] = torch.randn(M, kin - npix, device=DEV)
+    idx = torch.randint(0, M, (R,), device=DEV)
+    pix = torch.randn(R, npix, device=DEV)
+    wp = torch.zeros(N, (kin + 7) // 8 * 8, device=DEV)
+    wp[:, :kin] = torch.randn(N, kin, device=DEV) / math.sqrt(kin)
+    w = bf(wp)
+    lw, lb, bias = torch.randn(kin, device=DEV), torch.randn(kin, device=DEV), torch.randn(N, device=DEV)
+    outs = [K.ln_linear_fwd(pix, lw, lb, 1e-5, w, bias, 0, None, True, True, pe, kin, idx) for K in (_ext(), _emu())]
+    for a, b, n in zip(outs[0], outs[1], ("y", "mean", "rstd")):
+        close(a, b, 2e-2 if n == "y" else 1e-3, n)
+    y, mean, rstd = outs[1]
+    g = torch.randn(R, N, device=DEV)
+    res = []
+    for K in (_ext(), _emu()):
+        dg, dbn = torch.zeros(kin, device=DEV), torch.zeros(kin, device=DEV)
+        dW, dbias = torch.zeros(N, kin, device=DEV), torch.zeros(N, device=DEV)
+        K.ln_linear_bwd(g, w, pix, mean, rstd, lw, lb, None, False, dg, dbn, dW, dbias, pe, kin, pe_index=idx)
+        dW2, db2 = torch.ones(N, kin, device=DEV), torch.ones(N, device=DEV)
+        K.wgrad(g, pix, 1, mean, rstd, lw, lb, 0, dW2, db2, pe, kin, idx)
+        res.append((dg, dbn, dW, dbias, dW2, db2))
+    for a, b, n in zip(res[0], res[1], ("dgamma", "dbeta", "dW", "dbias", "wgrad dW", "wgrad db")):
+        close(a, b, 3e-2, n)
+
+
+def test_ln_linear_bwd_dx_in_place_of_dres():
+    """dx_out naming the dres buffer itself: dX = LN_bwd(g·w) + dres lands in place (the latent
+    array's gradient in the cross-attention backward)."""
+    torch.manual_seed(20)
+    R, N, Kin = 128, 64, 64
+    g = torch.randn(R, N, device=DEV)
+    w = bf(torch.randn(N, Kin, device=DEV) / math.sqrt(Kin))
+    x = torch.randn(R, Kin, device=DEV) * 1.5 + 0.2
+    lw, lb = torch.randn(Kin, device=DEV), torch.randn(Kin, device=DEV)
+    mean, rstd = x.mean(-1), torch.rsqrt(x.var(-1, unbiased=False) + 1e-5)
+    dres = torch.randn(R, Kin, device=DEV)
+    res = []
+    for K in (_ext(), _emu()):
+        buf = dres.clone()
+        dg, db = torch.zeros(Kin, device=DEV), torch.zeros(Kin, device=DEV)
+        dx = K.ln_linear_bwd(g, w, x, mean, rstd, lw, lb, buf, True, dg, db, None, None, dx_out=buf)
+        assert dx.data_ptr() == buf.data_ptr()
+        res.append((buf, dg, db))
+    for a, b, n in zip(res[0], res[1], ("dx", "dgamma", "dbeta")):
         close(a, b, 3e-2, n)
 
 

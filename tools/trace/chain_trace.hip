@@ -131,26 +131,32 @@ int main(int argc, char** argv) {
   CK(hipMalloc(&dY, (size_t)R * C * 4));
   CK(hipMalloc(&delta, (size_t)R * H * 4));
   CK(hipMalloc(&m2, R * 4)); CK(hipMalloc(&r2, R * 4)); CK(hipMalloc(&m1, R * 4)); CK(hipMalloc(&r1, R * 4));
-  pio::DropCfg dr{};
-  trace("sa_layer_fwd_chain", R, [&]() {
-    pio::sa_layer_fwd_launch(QKV, N, 0.36f, O, LSE, X, W[0], vec[0], vec[1], vec[2], 1e-5f, W[1], vec[3], W[2], vec[4],
-                             Z, Y, m2, r2, U, R, vec[5], vec[6], W[3], vec[7], QKVn, m1, r1, dr, 3 * C, 0);
-  });
+  pio::PostAttnParams pp{};
+  pp.Wo = W[0]; pp.bo = vec[0]; pp.g2 = vec[1]; pp.be2 = vec[2]; pp.eps = 1e-5f;
+  pp.W1 = W[1]; pp.b1 = vec[3]; pp.W2 = W[2]; pp.b2 = vec[4];
+  pio::PostAttnSaved sv{};
+  sv.Ysave = Y; sv.mean2 = m2; sv.rstd2 = r2; sv.Usave = U;
+  pio::NextProj np{};
+  np.lnw = vec[5]; np.lnb = vec[6]; np.Wq = W[3]; np.bq = vec[7]; np.QKVn = QKVn; np.mean1 = m1; np.rstd1 = r1;
+  np.nq = 3 * C;
+  pio::SaLayerFwdArgs f{};
+  f.QKV = QKV; f.N = N; f.scale_log2 = 0.36f; f.O = O; f.LSE = LSE; f.X = X; f.p = pp; f.Z = Z; f.s = sv; f.R = R;
+  f.next = np;
+  trace("sa_layer_fwd_chain", R, [&]() { pio::sa_layer_fwd_launch(f, 0); });
   // backward: inputs from the forward above
   float* G = dev_fill<float>((size_t)R * 3 * C, 1.f, false);
   float* dres = dev_fill<float>((size_t)R * C, 1.f, false);
   const int tiles = R / 64, P = (C + C + 3 * C * C + 3 * C) + (3 * C * C + 5 * C);
   CK(hipMalloc(&slab, (size_t)tiles * P * 4));
   float* s = slab;
-  float *dg1 = s, *db1 = s + C, *dwq = s + 2 * C, *dbq = s + 2 * C + 3 * C * C;
   float* pa = s + 2 * C + 3 * C * C + 3 * C;
-  pio::PostAttnGrads g{pa, pa + C * C, pa + C * C + C, pa + C * C + 2 * C, pa + C * C + 3 * C,
-                       pa + 2 * C * C + 3 * C, pa + 2 * C * C + 4 * C, pa + 3 * C * C + 4 * C, P, 1};
-  pio::SlabJob job{};
-  trace("ln_linear_post_attn_bwd_chain", R, [&]() {
-    pio::ln_linear_post_attn_bwd_launch(C, G, false, W[3], Z, m1, r1, vec[5], vec[6], dres, dg1, db1, dwq, dbq, Y, m2, r2, U, O,
-                                        W[0], W[1], W[2], vec[3], vec[4], dY, dO, delta, H, g, R, job, dr, 3 * C, 0);
-  });
+  pio::LnLinearPostAttnBwdArgs b{};
+  b.G = G; b.g_bf16 = false; b.next = np; b.X = Z; b.dres = dres;
+  b.dlnw = s; b.dlnb = s + C; b.dWq = s + 2 * C; b.dbq = s + 2 * C + 3 * C * C;
+  b.pa.s = sv; b.pa.O = O; b.pa.p = pp; b.pa.dY = dY; b.pa.dO = dO; b.pa.delta = delta; b.pa.H = H; b.pa.R = R;
+  b.pa.grads = pio::PostAttnGrads{pa, pa + C * C, pa + C * C + C, pa + C * C + 2 * C, pa + C * C + 3 * C,
+                                  pa + 2 * C * C + 3 * C, pa + 2 * C * C + 4 * C, pa + 3 * C * C + 4 * C, P, 1};
+  trace("ln_linear_post_attn_bwd_chain", R, [&]() { pio::ln_linear_post_attn_bwd_launch(b, C, 0); });
   // the same launch carrying the previous boundary's slab reduction (what the step runs)
   float* slab2;
   CK(hipMalloc(&slab2, (size_t)tiles * P * 4));
@@ -161,15 +167,13 @@ int main(int argc, char** argv) {
   job2.slab = slab2; job2.S = tiles; job2.P = P; job2.nbx = (P + pio::kSlabColsPerBlock - 1) / pio::kSlabColsPerBlock;
   { const int t = getenv("PIO_SLAB_WGS") ? atoi(getenv("PIO_SLAB_WGS")) : 128; int nsy = std::max(1, std::min(tiles, t / job2.nbx)); const int rb = (tiles + nsy - 1) / nsy; job2.nblk = job2.nbx * ((tiles + rb - 1) / rb); }
   job2.n = 1; job2.dst[0] = gdst; job2.off[0] = 0; job2.len[0] = P;
-  trace("ln_linear_post_attn_bwd_chain + slab job", R, [&]() {
-    pio::ln_linear_post_attn_bwd_launch(C, G, false, W[3], Z, m1, r1, vec[5], vec[6], dres, dg1, db1, dwq, dbq, Y, m2, r2, U, O,
-                                        W[0], W[1], W[2], vec[3], vec[4], dY, dO, delta, H, g, R, job2, dr, 3 * C, 0);
-  }, R / 64 + job2.nblk);
+  b.pa.job = job2;
+  trace("ln_linear_post_attn_bwd_chain + slab job", R, [&]() { pio::ln_linear_post_attn_bwd_launch(b, C, 0); },
+        R / 64 + job2.nblk);
   // G as bf16 (the attention backward's bf16 dQKV)
-  uint16_t* Gb = dev_fill<uint16_t>((size_t)R * 3 * C, 1.f, true);
-  trace("ln_linear_post_attn_bwd_chain bf16 G + slab job", R, [&]() {
-    pio::ln_linear_post_attn_bwd_launch(C, Gb, true, W[3], Z, m1, r1, vec[5], vec[6], dres, dg1, db1, dwq, dbq, Y, m2, r2,
-                                        U, O, W[0], W[1], W[2], vec[3], vec[4], dY, dO, delta, H, g, R, job2, dr, 3 * C, 0);
-  }, R / 64 + job2.nblk);
+  b.G = dev_fill<uint16_t>((size_t)R * 3 * C, 1.f, true);
+  b.g_bf16 = true;
+  trace("ln_linear_post_attn_bwd_chain bf16 G + slab job", R, [&]() { pio::ln_linear_post_attn_bwd_launch(b, C, 0); },
+        R / 64 + job2.nblk);
   return 0;
 }
