@@ -1877,6 +1877,44 @@ void lamb(Tensor p, Tensor g, Tensor m, Tensor v, OptT shadow, Tensor hyper, Ten
                    clip > 0 ? f32p(*norm_part) : nullptr, stream());
 }
 
+// weight EMA over a flat fp32 buffer (csrc/ema.hip): ema ← ema + hyper[5]·(w − ema); hyper[5] = 0
+// leaves ema untouched (steps that do not update, inside a static graph)
+void ema_update(Tensor ema, Tensor w, Tensor hyper) {
+  CHECK_CUDA(ema); CHECK_CUDA(w); CHECK_CUDA(hyper);
+  CHECK_DT(ema, torch::kFloat32); CHECK_DT(w, torch::kFloat32); CHECK_DT(hyper, torch::kFloat32);
+  TORCH_CHECK(ema.is_contiguous() && w.is_contiguous() && hyper.is_contiguous() && ema.numel() == w.numel() &&
+                  ema.get_device() == w.get_device() && ema.get_device() == hyper.get_device(),
+              "ema_update: ema and w contiguous fp32 of one size, on the device of hyper");
+  TORCH_CHECK(hyper.numel() >= 8, "ema_update: hyper of 8 floats (hyper[5] = 1 - decay)");
+  TORCH_CHECK(ema.numel() % 4 == 0, "ema_update: the element count must be a multiple of 4, got ", ema.numel());
+  TORCH_CHECK(((reinterpret_cast<uintptr_t>(ema.data_ptr()) | reinterpret_cast<uintptr_t>(w.data_ptr())) & 15) == 0,
+              "ema_update: the buffers must be 16-byte aligned");
+  TORCH_CHECK(ema.numel() == 0 || ema.data_ptr() != w.data_ptr(), "ema_update: ema and w must be different buffers");
+  pio::ema_update_launch(ema.data_ptr<float>(), f32p(w), ema.numel(), f32p(hyper), stream());
+}
+
+// w ↔ ema in place and (shadow given) shadow ← bf16(new w), one pass; applied twice it restores
+// all three buffers bitwise
+void ema_swap(Tensor w, Tensor ema, OptT shadow) {
+  CHECK_CUDA(w); CHECK_CUDA(ema);
+  CHECK_DT(w, torch::kFloat32); CHECK_DT(ema, torch::kFloat32);
+  TORCH_CHECK(w.is_contiguous() && ema.is_contiguous() && w.numel() == ema.numel() && w.get_device() == ema.get_device(),
+              "ema_swap: w and ema contiguous fp32 of one size on one device");
+  TORCH_CHECK(w.numel() % 4 == 0, "ema_swap: the element count must be a multiple of 4, got ", w.numel());
+  uint16_t* sp = nullptr;
+  if (shadow.has_value()) {
+    CHECK_CUDA(*shadow); CHECK_DT(*shadow, torch::kBFloat16);
+    TORCH_CHECK(shadow->is_contiguous() && shadow->numel() == w.numel() && shadow->get_device() == w.get_device(),
+                "ema_swap: shadow contiguous bf16 of w's size on its device");
+    sp = reinterpret_cast<uint16_t*>(shadow->data_ptr());
+  }
+  TORCH_CHECK(((reinterpret_cast<uintptr_t>(w.data_ptr()) | reinterpret_cast<uintptr_t>(ema.data_ptr())) & 15) == 0 &&
+                  (reinterpret_cast<uintptr_t>(sp) & 7) == 0,
+              "ema_swap: the buffers must be 16-byte aligned (the shadow 8-byte)");
+  TORCH_CHECK(w.numel() == 0 || w.data_ptr() != ema.data_ptr(), "ema_swap: w and ema must be different buffers");
+  pio::ema_swap_launch(w.data_ptr<float>(), ema.data_ptr<float>(), sp, w.numel(), stream());
+}
+
 // self-test of the device cross-lane reductions: (6, 64) = wave_sum, wave_max, half_sum,
 // half_max, xor16_sum, xor32_sum of a 64-element fp32 vector
 Tensor reduce_probe(Tensor x) {
@@ -2312,6 +2350,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("eps"), py::arg("clip"), py::arg("gscale"), py::arg("zero_grad") = false,
         py::arg("loss_src") = py::none(), py::arg("loss_ring") = py::none(), py::arg("norm_part") = py::none());
   m.attr("LAMB_CHUNK") = pio::lamb_chunk_elems();
+  m.def("ema_update", &ema_update, py::arg("ema"), py::arg("w"), py::arg("hyper"));
+  m.def("ema_swap", &ema_swap, py::arg("w"), py::arg("ema"), py::arg("shadow") = py::none());
+  m.attr("EMA_PASS_ELEMS") = pio::ema_pass_elems();
   m.def("cast_bf16", &cast_bf16);
   m.def("reduce_probe", &reduce_probe);
   m.def("fold_replicas", &fold_replicas);

@@ -349,6 +349,14 @@ int stage_step_launch(void* const* dst, const void* const* src, const long long*
                       const float* hyper, int nhyper, long long* seed_dst, const long long* seeds, int nseeds,
                       hipStream_t st);
 unsigned check_errors_elementwise(bool reset);
+// ---- ema.hip ----
+// elements one pass of the capped grid covers (larger buffers take the grid-stride loop)
+long long ema_pass_elems();
+// e ← e + hyper[5]·(w − e) over n fp32 elements (nothing touched when hyper[5] == 0); ema, w
+// 16-byte aligned and n % 4 == 0 (checked by the binding)
+void ema_update_launch(float* ema, const float* w, long long n, const float* hyper, hipStream_t st);
+// w ↔ ema in place, shadow (may be null) ← bf16(new w); 16-byte aligned (shadow 8), n % 4 == 0
+void ema_swap_launch(float* w, float* ema, uint16_t* shadow, long long n, hipStream_t st);
 // ---- lamb.hip ----
 int lamb_chunk_elems();
 // p, g, m, v 16-byte aligned, shadow 8-byte aligned (checked by the binding); C chunks, T tensors

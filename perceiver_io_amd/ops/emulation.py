@@ -857,6 +857,35 @@ def lamb(p, g, m, v, shadow, hyper, chunk_tab, tensor_tab, tensor_opt, partials,
             shadow[lo:hi].copy_(w.to(shadow.dtype))
 
 
+def ema_update(ema, w, hyper):
+    """csrc/ema.hip ema_update_kernel: ema ← ema + omd·(w − ema) with omd = hyper[5] (1 − decay of
+    this step), as three separately rounded fp32 operations; omd == 0 leaves ema untouched and
+    omd == 1 (decay = 0) copies w, which ema + (w − ema) misses by a rounding where the two are
+    more than a factor of two apart."""
+    if ema.numel() % 4:
+        raise ValueError(f"ema_update: the element count must be a multiple of 4, got {ema.numel()}")
+    omd = hyper[5].to(torch.float32)
+    if float(omd) == 0.0:
+        return
+    if float(omd) == 1.0:
+        ema.copy_(w)
+        return
+    d = w - ema
+    d.mul_(omd)
+    ema.add_(d)
+
+
+def ema_swap(w, ema, shadow=None):
+    """csrc/ema.hip ema_swap_kernel: w ↔ ema in place, shadow (optional) ← bf16(new w)."""
+    if w.numel() % 4:
+        raise ValueError(f"ema_swap: the element count must be a multiple of 4, got {w.numel()}")
+    t = w.clone()
+    w.copy_(ema)
+    ema.copy_(t)
+    if shadow is not None:
+        shadow.copy_(w.to(shadow.dtype).view(shadow.shape))
+
+
 def fold_replicas(grad, rep):
     n = rep.shape[1]
     grad[:n] += rep.sum(0)

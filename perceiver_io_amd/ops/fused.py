@@ -92,6 +92,14 @@ class WeightCache:
         self._d[id(p)] = [p._version, p.data_ptr(), t, p]
         return t
 
+    def rewritten(self, p: torch.Tensor, shadow: torch.Tensor):
+        """``p`` was rewritten in place together with ``shadow`` and its version bumped
+        (``ops.optim.WeightEMA.swap``): an entry bound to that shadow follows the new version;
+        every other entry sees the change and re-casts on its next use."""
+        ent = self._d.get(id(p))
+        if ent is not None and ent[3] is p and ent[2].data_ptr() == shadow.data_ptr():
+            ent[0], ent[1] = p._version, p.data_ptr()
+
     def clear(self):
         self._d.clear()
 

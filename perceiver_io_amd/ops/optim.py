@@ -24,9 +24,13 @@ device tensor refreshed before each step, which keeps the update capturable in a
 ``Lamb`` / ``FusedLamb`` add LAMB: the flat space knows where tensors begin (``offsets``), so the
 fused update takes per-tensor trust ratios and per-tensor weight decay from chunk tables
 (``lamb_tables``, csrc/lamb.hip).
+
+``WeightEMA`` keeps an exponential moving average of the weights as one more flat fp32 buffer,
+updated by one launch behind the fused update and swapped in for evaluation (csrc/ema.hip).
 """
 from __future__ import annotations
 
+import contextlib
 import math
 from typing import Iterable, List, Optional
 
@@ -194,14 +198,33 @@ class FusedAdamW(torch.optim.Optimizer):
         # loss (loss_out[0]) into loss_out[1][hyper[7]] (see StepEngine's loss ring)
         self.loss_out = None
         self.loss_slot = 0
+        self.ema = None  # attach_ema: a WeightEMA over self.flat, updated right behind every update
+
+    def attach_ema(self, ema: Optional["WeightEMA"]):
+        """Average the weights after every update: ``hyper[5]`` carries the step's 1 − decay and one
+        more launch (``ema_update``) follows the update kernel, inside a captured step too."""
+        if ema is not None and ema.flat is not self.flat:
+            raise ValueError("attach_ema: the WeightEMA must be built over this optimizer's FlatParameterSpace")
+        if ema is not None and self.bucket_mode:
+            raise RuntimeError("attach_ema: attach before the step engine is built (per-bucket updates are already on)")
+        self.ema = ema
+
+    def _ema_update(self, K):
+        if self.ema is not None:
+            K.ema_update(self.ema.avg, self.flat.data, self.hyper)
 
     # -- the update ---------------------------------------------------------------------
     def hyper_values(self):
-        """lr / step / betas of the NEXT update (and the step engine's loss-ring slot), in
-        ``self.hyper``'s layout."""
+        """lr / step / betas of the NEXT update (and the step engine's loss-ring slot; with an
+        attached :class:`WeightEMA` its 1 − decay of that step, else 0), in ``self.hyper``'s layout."""
         g = self.param_groups[0]
         b1, b2 = g["betas"]
-        return [float(g["lr"]), float(self._step + 1), 0.0, float(b1), float(b2), 0.0, 0.0, float(self.loss_slot)]
+        # every update, eager or replayed, stages these first: the place to refuse one that would
+        # train the average instead of the weights
+        if self.ema is not None and self.ema.swapped:
+            raise RuntimeError("optimizer step while the averaged weights are swapped in (WeightEMA.swap)")
+        omd = 0.0 if self.ema is None else self.ema.one_minus_decay(self._step + 1)
+        return [float(g["lr"]), float(self._step + 1), 0.0, float(b1), float(b2), omd, 0.0, float(self.loss_slot)]
 
     def stage_hyper(self):
         """Write lr / step / betas for the NEXT update into device memory (outside any graph)."""
@@ -212,9 +235,10 @@ class FusedAdamW(torch.optim.Optimizer):
             self.hyper.copy_(torch.tensor(vals))
 
     def bucket_updates_ok(self) -> bool:
-        """Per-bucket updates are exact only without a global gradient norm (clipping) and without
-        replicated gradient accumulators (a later fold would add into an updated range)."""
-        return self.max_grad_norm <= 0 and self.flat.grad_rep is None
+        """Per-bucket updates are exact only without a global gradient norm (clipping), without
+        replicated gradient accumulators (a later fold would add into an updated range) and without
+        a weight EMA (the side-stream updates would finish after its launch)."""
+        return self.max_grad_norm <= 0 and self.flat.grad_rep is None and self.ema is None
 
     def range_update(self, lo: int, hi: int):
         """Fused AdamW over flat elements [lo, hi) only (the same per-element arithmetic as the
@@ -246,6 +270,7 @@ class FusedAdamW(torch.optim.Optimizer):
                 zero_grad=zero_grad and self.flat.grad_rep is None,
                 loss_src=None if lo is None else lo[0], loss_ring=None if lo is None else lo[1],
                 norm_part=self.norm_part)
+        self._ema_update(K)
 
     @torch.no_grad()
     def step(self, closure=None, staged: bool = False):
@@ -430,6 +455,7 @@ class FusedLamb(FusedAdamW):
                self.grad_scale, zero_grad=zero_grad and f.grad_rep is None,
                loss_src=None if lo is None else lo[0], loss_ring=None if lo is None else lo[1],
                norm_part=self.norm_part)
+        self._ema_update(K)
 
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
@@ -438,3 +464,138 @@ class FusedLamb(FusedAdamW):
         wds, adapts = self._tensor_options()
         self.tensor_opt.copy_(torch.tensor([(wd, 1.0 if a else 0.0) for wd, a in zip(wds, adapts)],
                                            dtype=torch.float32).reshape(-1, 2))
+
+
+class WeightEMA:
+    """Exponential moving average of the trainable weights, for evaluation and export.
+
+    Over a :class:`FlatParameterSpace` the average is ONE more flat fp32 buffer ``avg`` (a copy of
+    ``flat.data``; padding stays zero), updated by one streaming launch (csrc/ema.hip) that a fused
+    optimizer issues right behind its update (``FusedAdamW.attach_ema``) — inside a captured step
+    too, where the step's ``1 − decay`` arrives through ``hyper[5]``.  Over a plain parameter list
+    (the eager ``--trainer.precision=32`` path) it keeps per-tensor copies and updates them with
+    torch ops (:meth:`update`).
+
+    The schedule is a pure function of the 1-based optimizer step ``t``, so resuming and the
+    graph path need no counter of their own: steps with ``t % update_every != 0`` do not update;
+    the others use ``u = t // update_every`` and ``d = min(decay, (1 + u) / (10 + u))`` with
+    ``warmup``, else ``d = decay``.  Each update is ``e ← e + (1 − d)·(w − e)``: difference,
+    product and sum rounded to fp32 one by one, on every path; ``d = 0`` copies the weights
+    (``e + (w − e)`` misses ``w`` by a rounding where the two are a factor of two apart).
+
+    :meth:`swap` exchanges the weights with their average in place (and rewrites the bf16 shadow
+    the fused kernels read), :meth:`averaged` does so around a block and swaps back in ``finally``
+    — bitwise, so captured graphs keep their pointers and training goes on unchanged."""
+
+    def __init__(self, flat_or_params, decay: float = 0.9999, warmup: bool = True, update_every: int = 1):
+        decay = float(decay)
+        if not 0.0 <= decay <= 1.0:  # also refuses NaN
+            raise ValueError(f"WeightEMA: decay must be in [0, 1], got {decay}")
+        if int(update_every) < 1:
+            raise ValueError(f"WeightEMA: update_every must be at least 1, got {update_every}")
+        self.decay, self.warmup, self.update_every = decay, bool(warmup), int(update_every)
+        self.swapped = False
+        if isinstance(flat_or_params, FlatParameterSpace):
+            self.flat: Optional[FlatParameterSpace] = flat_or_params
+            self.params = self.flat.params
+            self.avg = self.flat.data.clone()
+            self._avgs = self.flat.views(self.avg)
+            self._hyper = None  # update() outside an optimizer: its own hyper block
+        else:
+            self.flat = None
+            self.params = [p for p in flat_or_params if p.requires_grad]
+            if not self.params:
+                raise ValueError("no trainable parameters")
+            self.avg = None
+            self._avgs = [p.detach().clone() for p in self.params]
+
+    # -- schedule -----------------------------------------------------------------------------
+    def one_minus_decay(self, t: int) -> float:
+        """1 − decay of optimizer step ``t`` (1-based) as the fp32 value the update multiplies by
+        (formed in double, rounded once); 0.0 on the steps that do not update."""
+        t = int(t)
+        if t < 1 or t % self.update_every:
+            return 0.0
+        d = self.decay
+        if self.warmup:
+            u = t // self.update_every
+            d = min(d, (1.0 + u) / (10.0 + u))
+        return float(torch.tensor(1.0 - d, dtype=torch.float64).to(torch.float32))
+
+    # -- update (the fused optimizers launch theirs themselves) -------------------------------------
+    @torch.no_grad()
+    def update(self, t: int):
+        """Fold the current weights into the average as optimizer step ``t`` (1-based)."""
+        if self.swapped:
+            raise RuntimeError("WeightEMA.update while the averaged weights are swapped in")
+        omd = self.one_minus_decay(t)
+        if omd == 0.0:
+            return
+        if self.flat is not None:
+            K = ext.require() if self.flat.device.type == "cuda" else emulation
+            if self._hyper is None:
+                self._hyper = torch.zeros(8, dtype=torch.float32, device=self.flat.device)
+            self._hyper[5] = omd
+            K.ema_update(self.avg, self.flat.data, self._hyper)
+            return
+        for p, a in zip(self.params, self._avgs):
+            if omd == 1.0:
+                a.copy_(p.detach())
+                continue
+            d = p.detach() - a
+            d.mul_(omd)
+            a.add_(d)
+
+    # -- evaluation with the averaged weights ----------------------------------------------------
+    @torch.no_grad()
+    def swap(self):
+        """Exchange the weights and their average in place (a second call restores both bitwise).
+        Everything keyed on a parameter's version sees a change: versions are bumped, and the
+        weight-cache entries bound to the flat shadow — rewritten by the same launch — follow."""
+        if self.flat is not None:
+            f = self.flat
+            K = ext.require() if f.device.type == "cuda" else emulation
+            K.ema_swap(f.data, self.avg, f.shadow)
+            from .fused import weight_cache
+
+            shadows = f.views(f.shadow) if f.shadow is not None else [None] * len(f.params)
+            for p, s in zip(f.params, shadows):
+                torch.autograd.graph.increment_version(p)
+                if s is not None:
+                    weight_cache.rewritten(p, s)
+        else:
+            for p, a in zip(self.params, self._avgs):
+                t = p.detach().clone()
+                p.copy_(a)  # in place on the parameter itself: bumps its version
+                a.copy_(t)
+        self.swapped = not self.swapped
+
+    @contextlib.contextmanager
+    def averaged(self):
+        """Run the block with the averaged weights; the training weights come back in ``finally``."""
+        self.swap()
+        try:
+            yield self
+        finally:
+            self.swap()
+
+    # -- state ------------------------------------------------------------------------------------
+    def tensors(self) -> List[torch.Tensor]:
+        """The averaged tensors in ``params`` order (views of ``avg`` over a flat space).  While
+        swapped in, the average lives in the parameters and these hold the training weights."""
+        return list(self._avgs)
+
+    def state_dict(self) -> List[torch.Tensor]:
+        if self.swapped:
+            raise RuntimeError("WeightEMA.state_dict while the averaged weights are swapped in")
+        return [a.detach().clone() for a in self._avgs]
+
+    @torch.no_grad()
+    def load_state_dict(self, tensors):
+        if self.swapped:
+            raise RuntimeError("WeightEMA.load_state_dict while the averaged weights are swapped in")
+        tensors = list(tensors)
+        if len(tensors) != len(self._avgs):
+            raise ValueError(f"WeightEMA: {len(tensors)} tensors for {len(self._avgs)} parameters")
+        for a, t in zip(self._avgs, tensors):
+            a.copy_(t.reshape(a.shape))

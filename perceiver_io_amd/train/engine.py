@@ -158,15 +158,25 @@ class StepEngine:
     gradient it consumes).  Every graph of a step is captured before the step's first
     micro-batch runs (the capture warm-ups clear the gradient buffer).  ``graph_impl``:
     ``"cuda"`` (hipGraph; default on a GPU) or ``"closure"`` (:class:`ClosureGraph`, tests).
+
+    A weight EMA travels with a fused optimizer (``FusedAdamW.attach_ema``: its update is part of
+    ``device_update``, captured with it); ``ema`` is for the other optimizers, updated right after
+    ``opt.step()`` as optimizer step ``ema_step0`` + the steps taken here.
     """
 
     def __init__(self, loss_fn: Callable, optimizer, scheduler=None, reducer=None, device=None,
                  graph: bool = False, accumulate: int = 1, warmup_eager: int = 2, max_graphs: int = 12,
-                 state_hooks=None, graph_impl: Optional[str] = None, bucket_update: Optional[bool] = None):
+                 state_hooks=None, graph_impl: Optional[str] = None, bucket_update: Optional[bool] = None,
+                 ema=None, ema_step0: int = 0):
         from ..ops.optim import FusedAdamW
 
         self.loss_fn = loss_fn
         self.opt = optimizer
+        # a WeightEMA for an optimizer that is not fused (a fused one carries its own, attach_ema):
+        # updated right after opt.step() as optimizer step ema_step0 + (steps taken here)
+        self.ema = None if isinstance(optimizer, FusedAdamW) else ema
+        self.ema_step0 = int(ema_step0)
+        self._plain_steps = 0
         self.sched = scheduler
         self.reducer = reducer
         self.device = torch.device(device) if device is not None else torch.device("cpu")
@@ -232,6 +242,9 @@ class StepEngine:
                     if p.grad is not None:
                         p.grad.mul_(self.reducer.grad_scale())
             self.opt.step()
+            if self.ema is not None:
+                self._plain_steps += 1
+                self.ema.update(self.ema_step0 + self._plain_steps)
         if self.sched is not None:
             self.sched.step()
         if self.reducer is not None:

@@ -33,7 +33,7 @@ import torch
 from .. import ops
 from ..parallel import dist as pdist
 from .callbacks import Callback, LearningRateMonitor, ModelCheckpoint
-from .checkpoint import load_checkpoint, make_checkpoint, save_checkpoint
+from .checkpoint import averaged_state_dict, load_checkpoint, make_checkpoint, parameter_names, save_checkpoint
 from .engine import StepEngine, _to
 from .loggers import TensorBoardLogger
 
@@ -110,7 +110,8 @@ class Trainer:
                  resume_from_checkpoint: Optional[str] = None, profiler: Optional[str] = None, benchmark: bool = False,
                  deterministic: bool = False, detect_anomaly: bool = False, terminate_on_nan: Optional[bool] = None,
                  replace_sampler_ddp: bool = True, graph_capture: Optional[bool] = None, seed: Optional[int] = None,
-                 allreduce_dtype: Optional[str] = None, **ignored: Any):
+                 allreduce_dtype: Optional[str] = None, ema_decay: Optional[float] = None, ema_warmup: bool = True,
+                 ema_update_every: int = 1, ema_eval: bool = True, **ignored: Any):
         for k, v in ignored.items():
             if v not in (None, False, 0, 0.0, "", [], {}) and k not in _KNOWN_NOOP:
                 warnings.warn(f"Trainer flag {k}={v!r} has no effect in this framework")
@@ -150,6 +151,17 @@ class Trainer:
         if allreduce_dtype not in (None, "fp32", "float32", "bf16", "bfloat16"):
             raise ValueError(f"allreduce_dtype must be fp32 or bf16, got {allreduce_dtype!r}")
         self.allreduce_dtype = torch.bfloat16 if allreduce_dtype in ("bf16", "bfloat16") else None
+        # weight EMA (ops.optim.WeightEMA): ema_decay None = off; with ema_eval validation / test run
+        # with the averaged weights.  Every rank averages its own (identical) parameters.
+        if ema_decay is not None and not 0.0 <= float(ema_decay) <= 1.0:
+            raise ValueError(f"ema_decay must be in [0, 1], got {ema_decay!r}")
+        if int(ema_update_every or 1) < 1:
+            raise ValueError(f"ema_update_every must be at least 1, got {ema_update_every!r}")
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        self.ema_update_every = int(ema_update_every or 1)
+        self.ema_eval = bool(ema_eval)
+        self.ema = None  # built by fit
         if fast_dev_run:
             n = 1 if fast_dev_run is True else int(fast_dev_run)
             self.limit_train_batches = self.limit_val_batches = self.limit_test_batches = n
@@ -357,6 +369,17 @@ class Trainer:
                 reducer.broadcast_parameters(model)
             if not self.fused and self.gradient_clip_val:
                 warnings.warn("gradient clipping on the eager path uses torch.nn.utils.clip_grad_norm_")
+            self.ema = None
+            if self.ema_decay is not None:
+                from ..ops.optim import FusedAdamW, WeightEMA
+
+                # after the parameter broadcast: every rank starts from (and keeps) the same average
+                if isinstance(opt, FusedAdamW):  # one flat buffer, updated behind the fused update
+                    self.ema = WeightEMA(opt.flat, self.ema_decay, self.ema_warmup, self.ema_update_every)
+                    opt.attach_ema(self.ema)
+                else:  # per-tensor copies, updated after opt.step()
+                    self.ema = WeightEMA([p for p in model.parameters() if p.requires_grad], self.ema_decay,
+                                         self.ema_warmup, self.ema_update_every)
             ckpt_path = ckpt_path or self.resume_from_checkpoint
             if ckpt_path:
                 self._restore(ckpt_path)
@@ -365,7 +388,8 @@ class Trainer:
             # graph, restored before its replays
             hooks = (lambda: dict(self._step_logs), self._restore_step_logs)
             self._engine = StepEngine(self._training_loss, opt, sched, reducer=reducer, device=self.device,
-                                      graph=bool(use_graph), accumulate=self.accumulate, state_hooks=hooks)
+                                      graph=bool(use_graph), accumulate=self.accumulate, state_hooks=hooks,
+                                      ema=self.ema, ema_step0=self.global_step)
             if self.logger is not None and self.is_global_zero:
                 self.logger.log_hyperparams(dict(model.hparams))
             for cb in self.callbacks:
@@ -403,10 +427,13 @@ class Trainer:
             dataloaders = dataloaders or (datamodule.test_dataloader() if stage == "test" else datamodule.val_dataloader())
         self._attach(model, datamodule)
         if ckpt_path:
-            sd = load_checkpoint(ckpt_path)["state_dict"]
-            model.load_state_dict(sd)
+            ckpt = load_checkpoint(ckpt_path)
+            # a checkpoint written with a weight EMA is evaluated with its averaged weights
+            averaged = self.ema_eval and "ema_state_dict" in ckpt
+            model.load_state_dict(averaged_state_dict(ckpt) if averaged else ckpt["state_dict"])
         with self._backend_ctx():
-            res = self._run_eval(self._loader(dataloaders, False), stage)
+            # the weights just loaded are the ones to evaluate: no swap with a previous fit's average
+            res = self._run_eval(self._loader(dataloaders, False), stage, swap=not ckpt_path)
         if verbose and self.is_global_zero:
             print({k: round(v, 5) for k, v in res.items()}, file=sys.stderr)
         return [res]
@@ -414,6 +441,8 @@ class Trainer:
     # ---- loops ---------------------------------------------------------------------------
     _in_train = False
     _cur_bs = 1
+    ema = None  # the WeightEMA of the current fit (ema_decay set), else None
+    ema_eval = True
 
     def _restore_step_logs(self, logs):
         self._step_logs = dict(logs)
@@ -514,6 +543,8 @@ class Trainer:
                         p.grad.mul_(red.grad_scale())
         torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.gradient_clip_val)
         opt.step()
+        if self.ema is not None:
+            self.ema.update(self.global_step + 1)  # the step just taken, 1-based
         for s in self.lr_schedulers:
             s.step()
         if self._engine.reducer is not None:
@@ -523,9 +554,20 @@ class Trainer:
         return loss.detach()
 
     @torch.no_grad()
-    def _run_eval(self, dl, stage: str, limit: Optional[int] = None) -> Dict[str, float]:
+    def _run_eval(self, dl, stage: str, limit: Optional[int] = None, swap: bool = True) -> Dict[str, float]:
         if dl is None:
             return {}
+        ema = self.ema if swap and self.ema_eval else None
+        # the loop and the module's epoch-end hook (sample predictions) see the averaged weights;
+        # the callbacks (checkpoints) fire after the swap back, on the training weights
+        with ema.averaged() if ema is not None else contextlib.nullcontext():
+            res = self._eval_loop(dl, stage, limit)
+        if not self.sanity_checking and stage == "validation":
+            for cb in self.callbacks:
+                cb.on_validation_end(self, self.model)
+        return res
+
+    def _eval_loop(self, dl, stage: str, limit: Optional[int]) -> Dict[str, float]:
         model = self.model
         was = model.training
         model.eval()
@@ -554,15 +596,14 @@ class Trainer:
             self.log_scalars(res)
             if stage == "validation":
                 model.on_validation_epoch_end()
-                for cb in self.callbacks:
-                    cb.on_validation_end(self, model)
         model.train(was)
         return res
 
     # ---- checkpointing -------------------------------------------------------------------
     def save_checkpoint(self, path: str):
         cbs = {cb.state_key(): cb.state_dict() for cb in self.callbacks if cb.state_dict()}
-        ckpt = make_checkpoint(self.model, self.current_epoch, self.global_step, self.optimizers, self.lr_schedulers, cbs)
+        ckpt = make_checkpoint(self.model, self.current_epoch, self.global_step, self.optimizers, self.lr_schedulers, cbs,
+                               ema=self.ema)
         if self.is_global_zero:
             save_checkpoint(ckpt, path)
         pdist.barrier()
@@ -574,6 +615,14 @@ class Trainer:
             o.load_state_dict(s)
         for sc, s in zip(self.lr_schedulers, ckpt.get("lr_schedulers", [])):
             sc.load_state_dict(s)
+        if self.ema is not None:
+            names = parameter_names(self.model, self.ema.params)
+            esd = ckpt.get("ema_state_dict")
+            if esd is not None and all(n in esd for n in names):
+                self.ema.load_state_dict([esd[n] for n in names])
+            else:
+                warnings.warn(f"{path} holds no weight EMA: the average restarts from the checkpoint's weights")
+                self.ema.load_state_dict([p.detach() for p in self.ema.params])
         self.global_step = int(ckpt.get("global_step", 0))
         self.current_epoch = int(ckpt.get("epoch", 0)) + 1
         for cb in self.callbacks:
