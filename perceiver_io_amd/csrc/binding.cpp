@@ -22,12 +22,13 @@ hipStream_t stream() { return at::hip::getCurrentHIPStream(); }
 // checked builds: the device error words of every checked translation unit (bit 1: a token id
 // outside the embedding table, 2: a gather row outside its destination, 4: a class label
 // outside [0, V) ∪ {-100}, 8: a PE row index outside its table, 16: a batch_augment crop box that had to be
-// clamped into its source image); reset clears them
+// clamped into its source image, 32: a rand_augment op word outside its table); reset clears them
 int64_t check_errors(bool reset) {
   return (int64_t)(pio::check_errors_elementwise(reset) | pio::check_errors_mlm_head(reset) |
                    pio::check_errors_ce_head(reset) | pio::check_errors_topk_head(reset) |
                    pio::check_errors_rowgemm(reset) | pio::check_errors_pixel_head(reset) |
-                   pio::check_errors_soft_ce_head(reset) | pio::check_errors_augment(reset));
+                   pio::check_errors_soft_ce_head(reset) | pio::check_errors_augment(reset) |
+                   pio::check_errors_randaugment(reset));
 }
 bool checked_build() { return PIO_CHECKS != 0; }
 // checked builds, outside graph capture: wait for the kernel just launched and raise on any
@@ -41,7 +42,8 @@ void checked_sync(const char* what) {
   const int64_t e = check_errors(true);
   TORCH_CHECK(e == 0, "checked build: ", what, " saw out-of-range indices (error bits ", e,
               ": 1 token id >= vocab, 2 gather row out of range, 4 label outside [0, V) and != -100, 8 PE row index outside "
-              "the position-encoding table, 16 batch_augment crop box outside its source image)");
+              "the position-encoding table, 16 batch_augment crop box outside its source image, 32 rand_augment op word "
+              "outside its table)");
 }
 
 // deterministic mode (trainer flag ``deterministic``): every reduction that would
@@ -1506,6 +1508,35 @@ Tensor batch_augment(Tensor src, Tensor params, std::vector<double> mean, std::v
   return out;
 }
 
+// RandAugment of a raw uint8 channels-last batch (csrc/randaugment.hip): words (B, N, 8) fp32 on the device,
+// {op, v, m00, m01, m02, m10, m11, m12} per sample and layer, read by the kernels.  The ping-pong image and the
+// histogram block come from the current allocator: inside a capture, from the graph's private pool.
+Tensor rand_augment(Tensor src, Tensor words, int64_t fill) {
+  CHECK_CUDA(src); CHECK_CUDA(words);
+  CHECK_DT(src, torch::kUInt8); CHECK_DT(words, torch::kFloat32);
+  TORCH_CHECK(src.dim() == 4 && src.is_contiguous(), "rand_augment: src must be (B, H, W, C) uint8 contiguous");
+  const int64_t B = src.size(0), H = src.size(1), W = src.size(2), C = src.size(3);
+  TORCH_CHECK(B >= 1 && B < (1 << 16) && H >= 1 && W >= 1, "rand_augment: 1 <= B < 65536, a non-empty image");
+  TORCH_CHECK(C == 1 || C == 3, "rand_augment: 1 or 3 channels, got ", C);
+  const int64_t lim = (int64_t)1 << 30;
+  TORCH_CHECK(H < lim && W < lim && H * W * C < lim, "rand_augment: a sample must hold fewer than 2^30 elements");
+  TORCH_CHECK(words.dim() == 3 && words.size(0) == B && words.size(2) == 8 && words.is_contiguous() &&
+                  words.get_device() == src.get_device(),
+              "rand_augment: words must be (B, N, 8) fp32 contiguous on src's device");
+  const int64_t N = words.size(1);
+  TORCH_CHECK(N >= 1 && N <= 8, "rand_augment: 1 <= N <= 8 layers, got ", N);
+  TORCH_CHECK(fill >= 0 && fill <= 255, "rand_augment: fill must be a uint8 value");
+  Tensor out = torch::empty_like(src);
+  Tensor tmp = N > 1 ? torch::empty_like(src) : Tensor();
+  // a fill kernel on the stream (not a memset, which a captured graph would not replay): zero on every replay
+  Tensor hist = torch::zeros({N, B, C + 1, 256}, src.options().dtype(torch::kInt32));
+  pio::rand_augment_launch(src.data_ptr<uint8_t>(), f32p(words), out.data_ptr<uint8_t>(),
+                           N > 1 ? tmp.data_ptr<uint8_t>() : nullptr, hist.data_ptr<int>(), (int)B, (int)H, (int)W, (int)C,
+                           (int)N, (int)fill, stream());
+  // no checked_sync: an op word outside the table is identity; the checked build's bit 32 waits for check_errors
+  return out;
+}
+
 Tensor embed_fwd(Tensor ids, Tensor E, Tensor P, double scale) {
   TORCH_CHECK(ids.is_contiguous() && E.is_contiguous() && P.is_contiguous());
   CHECK_DT(ids, torch::kInt64);
@@ -2334,6 +2365,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("batch_mix", &batch_mix, py::arg("x"), py::arg("y"), py::arg("mix"));
   m.def("batch_augment", &batch_augment, py::arg("src"), py::arg("params"), py::arg("mean"), py::arg("std"),
         py::arg("out_h"), py::arg("out_w"));
+  m.def("rand_augment", &rand_augment, py::arg("src"), py::arg("words"), py::arg("fill") = 0);
   m.def("embed_fwd", &embed_fwd);
   m.def("embed_bwd", &embed_bwd, py::arg("ids"), py::arg("g"), py::arg("dE"), py::arg("dP"), py::arg("scale"),
         py::arg("job_slab") = py::none(), py::arg("job_dsts") = std::vector<Tensor>(),

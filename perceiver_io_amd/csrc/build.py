@@ -41,6 +41,8 @@ PER_FILE_FLAGS = {"chain.hip": _VGPR_FORM, "attention_pe.hip": _VGPR_FORM, "ce_h
                   # augment.hip is bit-compared with the host pipeline and its PyTorch emulation: every
                   # product, sum and quotient rounded on its own
                   "augment.hip": ["-ffp-contract=off"],
+                  # randaugment.hip's blend and affine coordinates are bit-compared with its emulation
+                  "randaugment.hip": ["-ffp-contract=off"],
                   # ema.hip is bit-compared with its emulation: difference, product and sum of the update
                   # rounded one by one
                   "ema.hip": ["-ffp-contract=off"]}

@@ -420,6 +420,13 @@ void pixel_predict_launch(int C, int K, const float* H, const float* W, const fl
 void nonzero_compact_launch(const float* img, int B, long long npix, long long cap, int S, int V, int* segcount,
                             float* values, int64_t* index, bool* kmask, int* count, hipStream_t st);
 unsigned check_errors_pixel_head(bool reset);
+// ---- randaugment.hip ----
+// N layers of words (B, N, 8) over src (B, H, W, C), C ∈ {1, 3}; the result is written to out.
+// tmp: a second image of src's size (unused when N == 1); hist: N·B·(C + 1)·256 int32, cleared on st
+// by the caller before this call
+void rand_augment_launch(const uint8_t* src, const float* words, uint8_t* out, uint8_t* tmp, int* hist, int B, int H,
+                         int W, int C, int N, int fill, hipStream_t st);
+unsigned check_errors_randaugment(bool reset);
 // ---- rowgemm.hip ----
 void ln_linear_fwd_launch(const LnLinearFwdArgs& a, hipStream_t st);
 void post_attn_fwd_launch(const PostAttnFwdArgs& a, int C, hipStream_t st);

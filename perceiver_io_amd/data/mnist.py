@@ -22,7 +22,7 @@ from typing import Optional, Union
 
 import torch
 
-from .augment import DeviceAugment
+from .augment import DeviceAugment, RandAugment
 from .registry import register_datamodule
 from .synthetic import SyntheticImages
 
@@ -89,6 +89,18 @@ class _RawImages(torch.utils.data.Dataset):
         return (x.unsqueeze(-1) if x.dim() == 2 else x), int(self.labels[i])
 
 
+def _rand_augment(hparams: dict, device_augment: bool, source_hw, ops: int, magnitude: int, fill: int):
+    """The ``RandAugment`` of a data module's ``rand_augment_*`` options (None when unset), which are
+    recorded in ``hparams`` only when set."""
+    if int(ops) <= 0:
+        return None
+    if not device_augment:
+        raise ValueError("rand_augment_ops > 0 needs device_augment=true (RandAugment runs on the raw uint8 batch "
+                         "on the device)")
+    hparams.update(rand_augment_ops=int(ops), rand_augment_magnitude=int(magnitude), rand_augment_fill=int(fill))
+    return RandAugment(source_hw, num_ops=int(ops), magnitude=int(magnitude), fill=int(fill))
+
+
 @register_datamodule
 class MNISTDataModule:
     name = "mnist"
@@ -97,19 +109,23 @@ class MNISTDataModule:
                  val_split: Union[int, float] = 10000, num_workers: int = 3, normalize: bool = True, pin_memory: bool = False,
                  batch_size: int = 32, seed: int = 42, shuffle: bool = True, drop_last: bool = False,
                  synthetic: Union[bool, str] = "auto", synthetic_size: int = 60000, device_augment: bool = False,
-                 hflip: float = 0.0):
+                 hflip: float = 0.0, rand_augment_ops: int = 0, rand_augment_magnitude: int = 9,
+                 rand_augment_fill: int = 0):
         self.hparams = dict(channels_last=channels_last, random_crop=random_crop, data_dir=data_dir, val_split=val_split,
                             num_workers=num_workers, normalize=normalize, pin_memory=pin_memory, batch_size=batch_size,
                             seed=seed, synthetic=synthetic)
         self.device_augment = bool(device_augment)
         self.augment = None
+        ra = _rand_augment(self.hparams, self.device_augment, (28, 28), rand_augment_ops, rand_augment_magnitude,
+                           rand_augment_fill)
         if self.device_augment:
             if not channels_last:
                 raise ValueError("device_augment=True needs channels_last=True (ops.batch_augment writes channels-last)")
             self.hparams.update(device_augment=True, hflip=hflip)
             side = random_crop or 28
             self.augment = DeviceAugment((28, 28), (side, side), mode="random_crop", hflip=hflip,
-                                         mean=(0.5,) if normalize else (0.0,), std=(0.5,) if normalize else (1.0,))
+                                         mean=(0.5,) if normalize else (0.0,), std=(0.5,) if normalize else (1.0,),
+                                         rand_augment=ra)
         self.channels_last, self.random_crop = channels_last, random_crop
         self.data_dir = data_dir or "."
         self.val_split, self.num_workers, self.normalize = val_split, num_workers, normalize
@@ -198,25 +214,31 @@ class SyntheticImageDataModule:
 
     def __init__(self, image_shape=(224, 224, 3), num_classes: int = 1000, size: int = 10000, batch_size: int = 32,
                  num_workers: int = 2, pin_memory: bool = False, seed: int = 0, device_augment: bool = False,
-                 source_shape=None, scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3), hflip: float = 0.5):
+                 source_shape=None, scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3), hflip: float = 0.5,
+                 rand_augment_ops: int = 0, rand_augment_magnitude: int = 9, rand_augment_fill: int = 0):
         """``device_augment=True``: uint8 sources of ``source_shape`` (default: ``image_shape`` + 32
         rows and columns), random-resized-cropped to ``image_shape``, flipped and normalized on
-        the device (``self.augment``)."""
+        the device (``self.augment``); ``rand_augment_ops > 0``: that many RandAugment layers on
+        the source first."""
         self.hparams = dict(image_shape=list(image_shape), num_classes=num_classes, size=size, batch_size=batch_size)
         self._image_shape = tuple(image_shape)
         self.num_classes = num_classes
         self.size, self.batch_size, self.num_workers, self.pin_memory, self.seed = size, batch_size, num_workers, pin_memory, seed
         self.device_augment = bool(device_augment)
         self.augment = None
+        if not self.device_augment:  # raises when RandAugment is asked for
+            _rand_augment(self.hparams, False, None, rand_augment_ops, rand_augment_magnitude, rand_augment_fill)
         if self.device_augment:
             h, w, c = self._image_shape
             self.source_shape = tuple(source_shape) if source_shape is not None else (h + 32, w + 32, c)
             if len(self.source_shape) != 3 or self.source_shape[2] != c:
                 raise ValueError(f"source_shape {self.source_shape} must be (Hs, Ws, {c})")
+            ra = _rand_augment(self.hparams, True, self.source_shape[:2], rand_augment_ops, rand_augment_magnitude,
+                               rand_augment_fill)
             self.hparams.update(device_augment=True, source_shape=list(self.source_shape), scale=list(scale),
                                 ratio=list(ratio), hflip=hflip)
             self.augment = DeviceAugment(self.source_shape[:2], (h, w), mode="random_resized_crop", scale=tuple(scale),
-                                         ratio=tuple(ratio), hflip=hflip, mean=(0.5,), std=(0.5,))
+                                         ratio=tuple(ratio), hflip=hflip, mean=(0.5,), std=(0.5,), rand_augment=ra)
 
     @property
     def image_shape(self):
@@ -257,7 +279,8 @@ class NpyImageDataModule:
     def __init__(self, data_dir: str, image_shape=(224, 224, 3), num_classes: int = 1000, batch_size: int = 32,
                  num_workers: int = 2, pin_memory: bool = False, shuffle: bool = True, drop_last: bool = False,
                  mode: str = "random_resized_crop", scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3), hflip: float = 0.5,
-                 eval_crop_pct: float = 0.875, mean=(0.5,), std=(0.5,)):
+                 eval_crop_pct: float = 0.875, mean=(0.5,), std=(0.5,), rand_augment_ops: int = 0,
+                 rand_augment_magnitude: int = 9, rand_augment_fill: int = 0):
         self.hparams = dict(data_dir=data_dir, image_shape=list(image_shape), num_classes=num_classes,
                             batch_size=batch_size, mode=mode, scale=list(scale), ratio=list(ratio), hflip=hflip,
                             eval_crop_pct=eval_crop_pct, mean=list(mean), std=list(std))
@@ -270,6 +293,10 @@ class NpyImageDataModule:
         self._aug = dict(mode=mode, scale=tuple(scale), ratio=tuple(ratio), hflip=hflip, eval_crop_pct=eval_crop_pct,
                          mean=tuple(mean), std=tuple(std))
         self.augment = None  # built in setup(): the source size comes from the files
+        # validated (and recorded in hparams) now; the RandAugment itself needs the source size too
+        self._ra = (int(rand_augment_ops), int(rand_augment_magnitude), int(rand_augment_fill))
+        if self._ra[0] > 0:
+            _rand_augment(self.hparams, True, (1, 1), *self._ra)
         self.ds_train = self.ds_val = None
 
     @property
@@ -302,7 +329,8 @@ class NpyImageDataModule:
         vimgs, vlabs = self._load("val")
         if timgs.shape[1:3] != vimgs.shape[1:3]:
             raise ValueError(f"train {timgs.shape[1:3]} and val {vimgs.shape[1:3]} image sizes differ")
-        self.augment = DeviceAugment(timgs.shape[1:3], self._image_shape[:2], **self._aug)
+        self.augment = DeviceAugment(timgs.shape[1:3], self._image_shape[:2], **self._aug,
+                                     rand_augment=_rand_augment({}, True, timgs.shape[1:3], *self._ra))
         self.ds_train, self.ds_val = _RawImages(timgs, tlabs), _RawImages(vimgs, vlabs)
 
     def _dl(self, ds, shuffle):

@@ -70,7 +70,8 @@ def check_device_errors(reset: bool = True) -> None:
     * checked builds (``PERCEIVER_CHECKED=1``): the index-validation words — token ids, gather
       rows and class labels outside their tables (the kernels clamped / skipped the access), and
       bit 16: a ``batch_augment`` crop box that reached outside its source image (clamped; the
-      call itself never raises for it).
+      call itself never raises for it), and bit 32: a ``rand_augment`` op word outside its table
+      (applied as identity).
       Outside a graph capture every checked launch raises at once (``checked_sync``); inside a
       replayed hipGraph nothing can.
 
@@ -94,7 +95,8 @@ def check_device_errors(reset: bool = True) -> None:
             raise RuntimeError(f"checked build: out-of-range indices seen on the device (error bits {c:#x}: "
                                "1 token id >= vocab, 2 gather row out of range, 4 label outside [0, V) and != -100, "
                                "8 PE row index outside the position-encoding table, "
-                               "16 batch_augment crop box outside its source image)")
+                               "16 batch_augment crop box outside its source image, "
+                               "32 rand_augment op word outside its table)")
 
 
 def use_hip(t: torch.Tensor) -> bool:
@@ -156,6 +158,31 @@ def batch_augment(src: torch.Tensor, params: torch.Tensor, mean, std, out_hw) ->
     from . import emulation
 
     return emulation.batch_augment(src, params, mean, std, out_hw)
+
+
+def rand_augment(src: torch.Tensor, words: torch.Tensor, fill: int = 0) -> torch.Tensor:
+    """RandAugment of a raw ``uint8`` channels-last batch ``src`` (B, H, W, C ∈ {1, 3}) → uint8 of the
+    same shape.  ``words`` (B, N, 8) fp32 holds per sample and layer ``{op, v, m00, m01, m02, m10,
+    m11, m12}`` (``data.augment.RandAugment.draw``): op 0 identity, 1 nearest-neighbour affine with
+    the inverse matrix ``m`` in the pixel-centre convention (outside → ``fill``), 2 brightness,
+    3 color, 4 contrast, 5 sharpness (factor ``v``), 6 posterize (``v`` bits), 7 solarize (threshold
+    ``v``), 8 autocontrast, 9 equalize; the layers run in order on uint8 intermediates.  An op word
+    outside the table is identity.  HIP path: two kernels per layer that read ``words`` from device
+    memory (``csrc/randaugment.hip``) — no host sync, and a replayed hipGraph augments with
+    whatever words were staged for that step; bit for bit ``emulation.rand_augment``."""
+    if src.dtype != torch.uint8 or src.dim() != 4 or src.shape[3] not in (1, 3) or not src.is_contiguous():
+        raise ValueError("rand_augment: src must be a contiguous (B, H, W, C) uint8 batch with 1 or 3 channels, got "
+                         f"{tuple(src.shape)} {src.dtype}")
+    if words.dim() != 3 or words.shape[0] != src.shape[0] or words.shape[1] < 1 or words.shape[2] != 8:
+        raise ValueError(f"rand_augment: words must be (B, N >= 1, 8), got {tuple(words.shape)}")
+    if not 0 <= int(fill) <= 255:
+        raise ValueError(f"rand_augment: fill must be a uint8 value, got {fill}")
+    if use_hip(src):
+        w = words.to(device=src.device, dtype=torch.float32).contiguous()
+        return ext.require().rand_augment(src, w, int(fill))
+    from . import emulation
+
+    return emulation.rand_augment(src, words, int(fill))
 
 
 from . import attention, fused, masking, mlm_head, optim  # noqa: E402,F401

@@ -745,6 +745,109 @@ def batch_augment(src, params, mean, std, out_hw):
     return ((v / torch.full((1,), 255.0, device=dev) - m) / sd).contiguous()
 
 
+# ---- RandAugment on raw uint8 images (the definition csrc/randaugment.hip implements) ----------
+# A layer word block is {op, v, m00, m01, m02, m10, m11, m12}; integer parts in int64 tensors,
+# blend and the affine coordinates in fp32 with every operation rounded on its own.
+RA_IDENTITY, RA_AFFINE, RA_BRIGHTNESS, RA_COLOR, RA_CONTRAST = 0, 1, 2, 3, 4
+RA_SHARPNESS, RA_POSTERIZE, RA_SOLARIZE, RA_AUTOCONTRAST, RA_EQUALIZE = 5, 6, 7, 8, 9
+
+
+def _ra_blend(x, d, f):
+    """``trunc(clamp(d + f·(x − d), 0, 255))`` in fp32 (NaN → 0) of integer tensors ``x``, ``d`` and
+    a 0-dim fp32 ``f`` → int64."""
+    xf = x.to(torch.float32)
+    df = d.to(torch.float32) if torch.is_tensor(d) else torch.full_like(xf, float(d))
+    t = df + f * (xf - df)
+    zero, top = torch.zeros_like(t), torch.full_like(t, 255.0)
+    return torch.where(t >= 0.0, torch.where(t <= 255.0, t, top), zero).to(torch.int64)
+
+
+def _ra_grey(x):
+    """ITU-R 601 luma in 16.16 fixed point (PIL's ``convert("L")``) of an (H, W, 3) int64 image;
+    a one-channel image is its own grey level."""
+    if x.shape[2] == 1:
+        return x[..., 0]
+    return (19595 * x[..., 0] + 38470 * x[..., 1] + 7471 * x[..., 2] + 32768) >> 16
+
+
+def _ra_layer(x, word, fill: int):
+    """One layer on an (H, W, C) int64 image with values 0..255; ``word``: (8,) fp32."""
+    H, W, C = x.shape
+    w0 = float(word[0])
+    op = int(w0) if (0.0 <= w0 <= 9.0 and w0 == math.floor(w0)) else -1  # NaN fails the comparisons
+    v = word[1]
+    if op == RA_AFFINE:
+        jj = torch.arange(W, dtype=torch.float32, device=x.device)[None, :] + 0.5
+        ii = torch.arange(H, dtype=torch.float32, device=x.device)[:, None] + 0.5
+        fx = ((word[2] * jj + word[3] * ii) + word[4]).floor()
+        fy = ((word[5] * jj + word[6] * ii) + word[7]).floor()
+        inside = (fx >= 0.0) & (fx < float(W)) & (fy >= 0.0) & (fy < float(H))  # NaN and ±inf are outside
+        ix = torch.where(inside, fx, torch.zeros_like(fx)).to(torch.int64)
+        iy = torch.where(inside, fy, torch.zeros_like(fy)).to(torch.int64)
+        return torch.where(inside[..., None], x[iy, ix], torch.full_like(x, int(fill)))
+    if op == RA_BRIGHTNESS:
+        return _ra_blend(x, 0, v)
+    if op == RA_COLOR:
+        return _ra_blend(x, _ra_grey(x)[..., None].expand(H, W, C), v) if C == 3 else x
+    if op == RA_CONTRAST:
+        n = H * W
+        m = (2 * _ra_grey(x).sum() + n) // (2 * n)
+        return _ra_blend(x, m.expand(H, W, C), v)
+    if op == RA_SHARPNESS:
+        s = x.clone()
+        if H > 2 and W > 2:
+            acc = 5 * x[1:-1, 1:-1]
+            for di in (0, 1, 2):
+                for dj in (0, 1, 2):
+                    if (di, dj) != (1, 1):
+                        acc = acc + x[di:H - 2 + di, dj:W - 2 + dj]
+            s[1:-1, 1:-1] = (acc + 6) // 13
+        return _ra_blend(x, s, v)
+    if op == RA_POSTERIZE:
+        fv = float(v)
+        bits = (int(fv) if fv <= 8.0 else 8) if fv >= 0.0 else 0  # clamped into 0..8, NaN → 0
+        return x & (~((1 << (8 - bits)) - 1) & 255)
+    if op == RA_SOLARIZE:
+        return torch.where(x.to(torch.float32) >= v, 255 - x, x)
+    if op == RA_AUTOCONTRAST:
+        flat = x.reshape(-1, C)
+        lo, hi = flat.min(0).values, flat.max(0).values
+        span = (hi - lo).clamp(min=1)
+        return torch.where(hi > lo, ((x - lo) * 255) // span, x)
+    if op == RA_EQUALIZE:
+        out = x.clone()
+        n = H * W
+        for c in range(C):
+            h = torch.bincount(x[..., c].reshape(-1), minlength=256)
+            nz = torch.nonzero(h).reshape(-1)
+            if nz.numel() <= 1:
+                continue
+            step = (n - int(h[nz[-1]])) // 255
+            if step == 0:
+                continue
+            lut = ((step // 2 + (torch.cumsum(h, 0) - h)) // step).clamp(max=255)
+            out[..., c] = lut[x[..., c]]
+        return out
+    return x  # identity, or an op word outside the table
+
+
+def rand_augment(src, words, fill: int = 0):
+    """RandAugment layers on a raw uint8 channels-last batch ``src`` (B, H, W, C ∈ {1, 3}) → uint8.
+    ``words`` (B, N, 8) fp32: layer l of sample b is ``{op, v, m00, m01, m02, m10, m11, m12}``; the
+    layers run in order, each on the uint8 result of the previous one; the statistics of contrast,
+    autocontrast and equalize are those of the layer's input.  The op table and every formula: the
+    header of ``csrc/randaugment.hip``, whose kernels equal this function bit for bit."""
+    B = src.shape[0]
+    w = words.detach().to(device=src.device, dtype=torch.float32)
+    out = torch.empty_like(src)
+    for b in range(B):
+        x = src[b].to(torch.int64)
+        for l in range(w.shape[1]):
+            x = _ra_layer(x, w[b, l], fill)
+        out[b] = x.to(torch.uint8)
+    return out
+
+
 def embed_fwd(ids, E, P, scale):
     return E[ids] * scale + P[: ids.shape[1]].unsqueeze(0)
 

@@ -181,6 +181,7 @@ class LitImageClassifier(LitClassifier):
         self.model = self.create_model()
         self._mix_rng = None
         self._aug_rng = None
+        self._ra_rng = None
         self.augment = None  # a DeviceAugment set directly (tests); else the data module's
 
     def create_model(self):
@@ -201,8 +202,9 @@ class LitImageClassifier(LitClassifier):
         return self.model(x), y
 
     # -- device-side augmentation ---------------------------------------------------------------
-    # batch layouts: (x, y), (x, y, mix) and (x, y, mix | None, aug); ``aug`` is the (B, 8) block of
-    # DeviceAugment.draw for a raw uint8 ``x``
+    # batch layouts: (x, y), (x, y, mix), (x, y, mix | None, aug) and (x, y, mix | None, aug, ra);
+    # ``aug`` is the (B, 8) block of DeviceAugment.draw for a raw uint8 ``x``, ``ra`` the
+    # (B, num_ops, 8) block of its RandAugment's draw
     def _host_rng(self, tag: int):
         import numpy as np
 
@@ -229,6 +231,13 @@ class LitImageClassifier(LitClassifier):
             self._aug_rng = self._host_rng(0x415547)
         return torch.from_numpy(self._require_augmenter().draw(self._aug_rng, int(B), train))
 
+    def draw_rand_augment(self, B: int, train: bool = True) -> torch.Tensor:
+        """This micro-batch's RandAugment words as a host tensor, from a generator of their own
+        (same seeding scheme as ``draw_augment``)."""
+        if self._ra_rng is None:
+            self._ra_rng = self._host_rng(0x52414E44)
+        return torch.from_numpy(self._require_augmenter().rand_augment.draw(self._ra_rng, int(B), train))
+
     def _require_augmenter(self):
         aug = self.augmenter
         if aug is None:
@@ -247,7 +256,13 @@ class LitImageClassifier(LitClassifier):
             aug = batch[3] if len(batch) > 3 else None
             if aug is None:
                 aug = self.draw_augment(x.shape[0], self.training)
-            x = augmenter.apply(x, aug)
+            if getattr(augmenter, "rand_augment", None) is None:
+                x = augmenter.apply(x, aug)
+            else:  # eager evaluation: no RandAugment call at all
+                ra = batch[4] if len(batch) > 4 else None
+                if ra is None and self.training:
+                    ra = self.draw_rand_augment(x.shape[0])
+                x = augmenter.apply(x, aug, ra)
         return x, y, mix
 
     # -- MixUp / CutMix ------------------------------------------------------------------------
@@ -272,14 +287,18 @@ class LitImageClassifier(LitClassifier):
 
     def graph_batch(self, batch):
         """Graph path: the host draws travel inside the batch — ``(x, y, mix)`` when mixing,
-        ``(x, y, mix | None, aug)`` for a raw uint8 ``x`` — so the step engine stages them into the
-        captured graph's static inputs and every replay mixes / augments with fresh values."""
+        ``(x, y, mix | None, aug)`` for a raw uint8 ``x``, ``(x, y, mix | None, aug, ra)`` when the
+        augmenter has a RandAugment — so the step engine stages them into the captured graph's
+        static inputs and every replay mixes / augments with fresh values."""
         if len(batch) != 2:
             return batch
         x, y = batch
         mix = self.draw_mix().to(x.device, non_blocking=True) if self.mixing else None
         if x.dtype == torch.uint8:
-            return x, y, mix, self.draw_augment(x.shape[0], True).to(x.device, non_blocking=True)
+            aug = self.draw_augment(x.shape[0], True).to(x.device, non_blocking=True)
+            if getattr(self._require_augmenter(), "rand_augment", None) is None:
+                return x, y, mix, aug
+            return x, y, mix, aug, self.draw_rand_augment(x.shape[0]).to(x.device, non_blocking=True)
         return batch if mix is None else (x, y, mix)
 
     def soft_inputs(self, batch):
