@@ -1606,7 +1606,7 @@ std::vector<Tensor> text_mask(Tensor x, OptT pad, Tensor state, int64_t unk, int
 // seed_dst + seeds: a captured step's dropout seed slots (int64, ≤ 64 values) written in the same launch
 void stage_step(std::vector<Tensor> dsts, std::vector<Tensor> srcs, OptT hyper_dst, std::vector<double> hyper,
                 OptT seed_dst, std::vector<int64_t> seeds) {
-  TORCH_CHECK(dsts.size() == srcs.size() && dsts.size() <= 8 && hyper.size() <= 8, "stage_step: at most 8 tensors / 8 values");
+  TORCH_CHECK(dsts.size() == srcs.size() && dsts.size() <= 8 && hyper.size() <= 40, "stage_step: at most 8 tensors / 40 values");
   std::vector<void*> d;
   std::vector<const void*> x;
   std::vector<long long> n;
@@ -1863,7 +1863,7 @@ void adamw(Tensor p, Tensor g, Tensor m, Tensor v, OptT shadow, Tensor hyper, do
 // partials: >= 2 C fp32 (per-chunk Σw², Σu²), trust: (T,) fp32 (written every step, kept)
 void lamb(Tensor p, Tensor g, Tensor m, Tensor v, OptT shadow, Tensor hyper, Tensor chunk_tab, Tensor tensor_tab,
           Tensor tensor_opt, Tensor partials, Tensor trust, double eps, double clip, double gscale, bool zero_grad,
-          OptT loss_src, OptT loss_ring, OptT norm_part) {
+          OptT loss_src, OptT loss_ring, OptT norm_part, OptT tensor_group) {
   TORCH_CHECK(clip <= 0 || (norm_part.has_value() && norm_part->is_contiguous() && norm_part->numel() >= kSumsqParts &&
                             norm_part->scalar_type() == torch::kFloat32),
               "lamb: clip > 0 needs norm_part (the sumsq partials of the gradient)");
@@ -1898,6 +1898,16 @@ void lamb(Tensor p, Tensor g, Tensor m, Tensor v, OptT shadow, Tensor hyper, Ten
     TORCH_CHECK(loss_src->numel() == 1 && loss_ring->is_contiguous() && loss_ring->numel() >= 1,
                 "lamb: scalar loss_src, contiguous loss_ring, hyper[7] = ring slot");
   }
+  // per-tensor lr: tensor_group (T,) int32 picks hyper[8 + 4 j]; the group count follows from hyper's width
+  const int* tg = nullptr;
+  int G = 1;
+  if (tensor_group.has_value()) {
+    CHECK_CUDA(*tensor_group); CHECK_DT(*tensor_group, torch::kInt32);
+    G = (int)((hyper.numel() - 8) / 4);
+    TORCH_CHECK(tensor_group->is_contiguous() && tensor_group->numel() == T && hyper.is_contiguous() && G >= 1 && G <= 8,
+                "lamb: tensor_group (T,) int32 with hyper of 8 + 4 G floats, 1 <= G <= 8");
+    tg = tensor_group->data_ptr<int>();
+  }
   pio::lamb_launch(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), sp, p.numel(),
                    f32p(hyper), reinterpret_cast<const long long*>(chunk_tab.data_ptr<int64_t>()), C,
                    tensor_tab.data_ptr<int>(), f32p(tensor_opt), (int)T, partials.data_ptr<float>(),
@@ -1905,7 +1915,54 @@ void lamb(Tensor p, Tensor g, Tensor m, Tensor v, OptT shadow, Tensor hyper, Ten
                    loss_src.has_value() ? f32p(*loss_src) : nullptr,
                    loss_ring.has_value() ? loss_ring->data_ptr<float>() : nullptr,
                    loss_ring.has_value() ? (int)loss_ring->numel() : 1,
-                   clip > 0 ? f32p(*norm_part) : nullptr, stream());
+                   clip > 0 ? f32p(*norm_part) : nullptr, tg, G, stream());
+}
+
+// AdamW with per-group lr / weight decay / eps (elementwise.hip adamw_grouped_kernel): chunk_tab (C, 3)
+// int64 = (start, length, tensor) as for lamb, tensor_group (T,) int32, hyper = 8 global words + 4 per
+// group (lr, weight decay, eps, reserved)
+void adamw_grouped(Tensor p, Tensor g, Tensor m, Tensor v, OptT shadow, Tensor hyper, Tensor chunk_tab,
+                   Tensor tensor_group, int64_t groups, double clip, double gscale, bool l2, bool zero_grad, OptT loss_src,
+                   OptT loss_ring, OptT norm_part) {
+  TORCH_CHECK(clip <= 0 || (norm_part.has_value() && norm_part->is_contiguous() && norm_part->numel() >= kSumsqParts &&
+                            norm_part->scalar_type() == torch::kFloat32),
+              "adamw_grouped: clip > 0 needs norm_part (the sumsq partials of the gradient)");
+  CHECK_CUDA(p); CHECK_CUDA(g); CHECK_CUDA(m); CHECK_CUDA(v); CHECK_CUDA(hyper); CHECK_CUDA(chunk_tab);
+  CHECK_CUDA(tensor_group);
+  CHECK_DT(p, torch::kFloat32); CHECK_DT(g, torch::kFloat32); CHECK_DT(m, torch::kFloat32); CHECK_DT(v, torch::kFloat32);
+  CHECK_DT(hyper, torch::kFloat32); CHECK_DT(chunk_tab, torch::kInt64); CHECK_DT(tensor_group, torch::kInt32);
+  TORCH_CHECK(p.is_contiguous() && g.is_contiguous() && m.is_contiguous() && v.is_contiguous());
+  TORCH_CHECK(p.numel() == g.numel() && p.numel() == m.numel() && p.numel() == v.numel());
+  uint16_t* sp = nullptr;
+  if (shadow.has_value()) {
+    CHECK_DT(*shadow, torch::kBFloat16);
+    TORCH_CHECK(shadow->is_contiguous() && shadow->numel() == p.numel());
+    sp = reinterpret_cast<uint16_t*>(shadow->data_ptr());
+  }
+  TORCH_CHECK(((reinterpret_cast<uintptr_t>(p.data_ptr()) | reinterpret_cast<uintptr_t>(g.data_ptr()) |
+                reinterpret_cast<uintptr_t>(m.data_ptr()) | reinterpret_cast<uintptr_t>(v.data_ptr())) & 15) == 0 &&
+                  (reinterpret_cast<uintptr_t>(sp) & 7) == 0,
+              "adamw_grouped: the flat buffers must be 16-byte aligned (the shadow 8-byte)");
+  const int64_t C = chunk_tab.size(0), T = tensor_group.numel();
+  TORCH_CHECK(chunk_tab.dim() == 2 && chunk_tab.size(1) == 3 && chunk_tab.is_contiguous() && tensor_group.is_contiguous() &&
+                  C < (int64_t(1) << 31) && T < (int64_t(1) << 31),
+              "adamw_grouped: chunk_tab (C, 3) int64, tensor_group (T,) int32, contiguous");
+  TORCH_CHECK(groups >= 1 && groups <= 8 && hyper.is_contiguous() && hyper.numel() >= 8 + 4 * groups,
+              "adamw_grouped: 1 <= groups <= 8 and hyper of 8 + 4 * groups floats");
+  TORCH_CHECK(loss_src.has_value() == loss_ring.has_value(), "adamw_grouped: loss_src and loss_ring go together");
+  if (loss_src.has_value()) {
+    CHECK_DT(*loss_src, torch::kFloat32); CHECK_DT(*loss_ring, torch::kFloat32);
+    TORCH_CHECK(loss_src->numel() == 1 && loss_ring->is_contiguous() && loss_ring->numel() >= 1,
+                "adamw_grouped: scalar loss_src, contiguous loss_ring, hyper[7] = ring slot");
+  }
+  TORCH_CHECK(pio::adamw_grouped_launch(
+                  p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), sp, p.numel(),
+                  f32p(hyper), reinterpret_cast<const long long*>(chunk_tab.data_ptr<int64_t>()), C,
+                  tensor_group.data_ptr<int>(), (int)T, (int)groups, (float)clip, (float)gscale, l2 ? 1 : 0,
+                  zero_grad ? 1 : 0, loss_src.has_value() ? f32p(*loss_src) : nullptr,
+                  loss_ring.has_value() ? loss_ring->data_ptr<float>() : nullptr,
+                  loss_ring.has_value() ? (int)loss_ring->numel() : 1, clip > 0 ? f32p(*norm_part) : nullptr,
+                  stream()) == 0);
 }
 
 // weight EMA over a flat fp32 buffer (csrc/ema.hip): ema ← ema + hyper[5]·(w − ema); hyper[5] = 0
@@ -2380,7 +2437,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lamb", &lamb, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("shadow"), py::arg("hyper"),
         py::arg("chunk_tab"), py::arg("tensor_tab"), py::arg("tensor_opt"), py::arg("partials"), py::arg("trust"),
         py::arg("eps"), py::arg("clip"), py::arg("gscale"), py::arg("zero_grad") = false,
-        py::arg("loss_src") = py::none(), py::arg("loss_ring") = py::none(), py::arg("norm_part") = py::none());
+        py::arg("loss_src") = py::none(), py::arg("loss_ring") = py::none(), py::arg("norm_part") = py::none(),
+        py::arg("tensor_group") = py::none());
+  m.def("adamw_grouped", &adamw_grouped, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("shadow"),
+        py::arg("hyper"), py::arg("chunk_tab"), py::arg("tensor_group"), py::arg("groups"), py::arg("clip"),
+        py::arg("gscale"), py::arg("l2") = false, py::arg("zero_grad") = false, py::arg("loss_src") = py::none(),
+        py::arg("loss_ring") = py::none(), py::arg("norm_part") = py::none());
   m.attr("LAMB_CHUNK") = pio::lamb_chunk_elems();
   m.def("ema_update", &ema_update, py::arg("ema"), py::arg("w"), py::arg("hyper"));
   m.def("ema_swap", &ema_swap, py::arg("w"), py::arg("ema"), py::arg("shadow") = py::none());

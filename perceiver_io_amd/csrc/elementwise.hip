@@ -353,6 +353,111 @@ __global__ __launch_bounds__(256) void adamw4_kernel(float4* __restrict__ p, flo
   }
 }
 
+// AdamW with per-group lr / weight decay / eps (ops/optim.py FusedAdamW with several parameter
+// groups).  The flat buffers carry no tensor boundaries, so the host hands over the chunk table of
+// the LAMB update (chunks (C, 3) int64 = start, length, tensor: at most kAdamChunk elements, never
+// across a tensor boundary, the padding between tensors in no chunk) and tgroup (T,) int32 =
+// tensor → group.  Group j's words sit behind the 8 global ones: hyper[8 + 4j .. ] = lr, weight
+// decay, eps, reserved.  step / betas / clip factor / gscale / l2 / zero_g / loss ring are global,
+// and every element takes adamw4_kernel's arithmetic (adamw_elem), so with equal options in
+// every group the result is bitwise adamw4_kernel's.  A workgroup walks chunks grid-stride: 256
+// threads × float4, every load of a chunk in flight before the arithmetic, a scalar tail for
+// length % 4.  Padding is neither read nor written; no atomics.  A chunk that does not fit the
+// buffers or a group id outside [0, G) is skipped (checked builds flag kErrOptTable).
+constexpr int kAdamChunk = 4096;                  // elements; ops/optim.py LAMB_CHUNK
+constexpr int kAdamIter = kAdamChunk / (4 * 256);  // float4 per thread of a full chunk
+constexpr int kAdamGroupBase = 8, kAdamGroupWords = 4, kAdamMaxGroups = 8;
+
+// adamw4_kernel's update of one element with the multiply-adds the compiler fuses there under
+// -ffp-contract=fast spelled out (decay = fma(−wd, lr, 1), m ← fma(β1, m, (1−β1)·ĝ), v ← fma(β2, v,
+// ((1−β2)·ĝ)·ĝ), everything else rounded on its own) and contraction off, so that the vector path
+// and the tail of the grouped kernel cannot come out differently from it or from each other
+// (tests/test_param_groups_gpu.py compares the two kernels bit for bit)
+__device__ __forceinline__ void adamw_elem(float pi, float g0, float mi, float vi, float gs, float wd, float decay,
+                                           float beta1, float omb1, float beta2, float omb2, float step_size, float bc2s,
+                                           float eps, int l2, float& po, float& mo, float& vo) {
+#pragma clang fp contract(off)
+  const float gi = l2 ? fmaf(wd, pi, g0 * gs) : g0 * gs;
+  if (!l2) pi *= decay;
+  mo = fmaf(beta1, mi, omb1 * gi);
+  vo = fmaf(beta2, vi, (omb2 * gi) * gi);
+  po = pi - step_size * mo / (sqrtf(vo) / bc2s + eps);
+}
+
+__global__ __launch_bounds__(256) void adamw_grouped_kernel(
+    float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+    uint16_t* __restrict__ shadow, long long n, const float* __restrict__ hyper, const long long* __restrict__ chunks,
+    long long C, const int* __restrict__ tgroup, int T, int G, float clip, float gscale, int l2, int zero_g,
+    const float* __restrict__ loss_src, float* __restrict__ loss_ring, int ring_n, const float* __restrict__ norm_part) {
+  const float step = hyper[1], beta1 = hyper[3], beta2 = hyper[4];
+  if (loss_src != nullptr && blockIdx.x == 0 && threadIdx.x == 0) loss_ring[(int)hyper[7] % ring_n] = *loss_src;
+  const float bc1 = 1.f - powf(beta1, step), bc2 = 1.f - powf(beta2, step);
+  float gs = gscale;
+  if (clip > 0.f) gs *= adam_clip_scale(norm_part, clip, gscale);
+  const float bc2s = sqrtf(bc2), omb1 = 1.f - beta1, omb2 = 1.f - beta2;
+  for (long long c = blockIdx.x; c < C; c += gridDim.x) {  // uniform over the block
+    const long long start = chunks[3 * c], len = chunks[3 * c + 1], tid = chunks[3 * c + 2];
+    bool ok = start >= 0 && (start & 3) == 0 && len >= 0 && len <= kAdamChunk && start + len <= n && tid >= 0 && tid < T;
+    const int grp = ok ? tgroup[tid] : 0;
+    ok = ok && grp >= 0 && grp < G;
+    if (!ok) {
+      if (threadIdx.x == 0) pio_flag(kErrOptTable);
+      continue;
+    }
+    const float* hg = hyper + kAdamGroupBase + kAdamGroupWords * grp;
+    const float lr = hg[0], wd = hg[1], eps = hg[2];
+    const float step_size = lr / bc1, decay = fmaf(-wd, lr, 1.f);
+    const int len4 = (int)len >> 2;
+    float4* p4 = reinterpret_cast<float4*>(p + start);
+    float4* g4 = reinterpret_cast<float4*>(g + start);
+    float4* m4 = reinterpret_cast<float4*>(m + start);
+    float4* v4 = reinterpret_cast<float4*>(v + start);
+    uint2* s2 = shadow ? reinterpret_cast<uint2*>(shadow + start) : nullptr;
+    float4 P[kAdamIter], Gr[kAdamIter], M[kAdamIter], V[kAdamIter];
+#pragma unroll
+    for (int k = 0; k < kAdamIter; ++k) {
+      const int i = threadIdx.x + 256 * k;
+      if (i < len4) {
+        P[k] = p4[i];
+        Gr[k] = g4[i];
+        M[k] = m4[i];
+        V[k] = v4[i];
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < kAdamIter; ++k) {
+      const int i = threadIdx.x + 256 * k;
+      if (i < len4) {
+        if (zero_g) g4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        const float pa[4] = {P[k].x, P[k].y, P[k].z, P[k].w}, ga[4] = {Gr[k].x, Gr[k].y, Gr[k].z, Gr[k].w};
+        const float ma[4] = {M[k].x, M[k].y, M[k].z, M[k].w}, va[4] = {V[k].x, V[k].y, V[k].z, V[k].w};
+        float po[4], mo[4], vo[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          adamw_elem(pa[e], ga[e], ma[e], va[e], gs, wd, decay, beta1, omb1, beta2, omb2, step_size, bc2s, eps, l2, po[e],
+                     mo[e], vo[e]);
+        m4[i] = make_float4(mo[0], mo[1], mo[2], mo[3]);
+        v4[i] = make_float4(vo[0], vo[1], vo[2], vo[3]);
+        p4[i] = make_float4(po[0], po[1], po[2], po[3]);
+        if (s2) s2[i] = make_uint2(pack2(po[0], po[1]), pack2(po[2], po[3]));
+      }
+    }
+    // a tensor's last chunk: up to 3 elements past the last whole float4
+    const int t = (len4 << 2) + threadIdx.x;
+    if (t < (int)len) {
+      const long long j = start + t;
+      const float g0 = g[j];
+      if (zero_g) g[j] = 0.f;
+      float pi, mi, vi;
+      adamw_elem(p[j], g0, m[j], v[j], gs, wd, decay, beta1, omb1, beta2, omb2, step_size, bc2s, eps, l2, pi, mi, vi);
+      m[j] = mi;
+      v[j] = vi;
+      p[j] = pi;
+      if (shadow) shadow[j] = f2bf(pi);
+    }
+  }
+}
+
 __global__ void cast_bf16_kernel(const float* __restrict__ x, uint16_t* __restrict__ y, long long n) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
     y[i] = f2bf(x[i]);
@@ -519,6 +624,19 @@ void adamw_launch(float* p, float* g, float* m, float* v, uint16_t* shadow, long
     hipLaunchKernelGGL(adamw_kernel, grid_for(n), dim3(256), 0, st, p, g, m, v, shadow, n, hyper, eps, wd, clip, gscale,
                        l2, zero_g, loss_src, loss_ring, ring_n, norm_part);
 }
+// p, g, m, v 16-byte aligned, shadow 8-byte aligned, hyper of 8 + 4 G floats (checked by the
+// binding); C chunks, T tensors, 1 ≤ G ≤ 8.  At most 2048 workgroups (8 per CU) walk the chunks.
+int adamw_grouped_launch(float* p, float* g, float* m, float* v, uint16_t* shadow, long long n, const float* hyper,
+                         const long long* chunks, long long C, const int* tgroup, int T, int G, float clip, float gscale,
+                         int l2, int zero_g, const float* loss_src, float* loss_ring, int ring_n,
+                         const float* norm_part, hipStream_t st) {
+  if (G < 1 || G > kAdamMaxGroups) return -1;
+  if (C <= 0 || T <= 0) return 0;
+  const unsigned blocks = (unsigned)(C < 2048 ? C : 2048);
+  hipLaunchKernelGGL(adamw_grouped_kernel, dim3(blocks), dim3(256), 0, st, p, g, m, v, shadow, n, hyper, chunks, C, tgroup,
+                     T, G, clip, gscale, l2, zero_g, loss_src, loss_ring, ring_n, norm_part);
+  return 0;
+}
 // grad[i] += Σ_r rep[r][i], rep[r][i] ← 0 (replicated gradient accumulators, see ops/optim.py)
 __global__ void fold_replicas_kernel(float* __restrict__ grad, float* __restrict__ rep, long long n, int nrep) {
   const long long n4 = n >> 2;
@@ -585,7 +703,8 @@ void cast_bf16_launch(const float* x, uint16_t* y, long long n, hipStream_t st) 
 // 16-byte units, the others byte-wise.
 // ------------------------------------------------------------------------------------------
 namespace pio {
-constexpr int kStageSegs = 8, kStageHyper = 8, kStageSeeds = 64;
+// kStageHyper: the optimizer's 8 global words + 4 per parameter group, at most 8 groups
+constexpr int kStageSegs = 8, kStageHyper = 40, kStageSeeds = 64;
 struct StageArgs {
   void* dst[kStageSegs];
   const void* src[kStageSegs];

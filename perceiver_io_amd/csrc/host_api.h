@@ -341,6 +341,12 @@ void batch_sum2_launch(const float* a, const float* b, float* oa, float* ob, int
 void adamw_launch(float* p, float* g, float* m, float* v, uint16_t* shadow, long long n, const float* hyper,
                   float eps, float wd, float clip, float gscale, int l2, int zero_g, const float* loss_src,
                   float* loss_ring, int ring_n, const float* norm_part, hipStream_t st);
+// AdamW with per-group lr / weight decay / eps over the LAMB chunk table (chunks (C, 3) int64,
+// tgroup (T,) int32 = tensor → group, hyper of 8 + 4 G floats); -1 for G outside [1, 8]
+int adamw_grouped_launch(float* p, float* g, float* m, float* v, uint16_t* shadow, long long n, const float* hyper,
+                         const long long* chunks, long long C, const int* tgroup, int T, int G, float clip, float gscale,
+                         int l2, int zero_g, const float* loss_src, float* loss_ring, int ring_n,
+                         const float* norm_part, hipStream_t st);
 void fold_replicas_launch(float* grad, float* rep, long long n, int nrep, hipStream_t st);
 void slab_reduce_launch(const SlabJob& job, hipStream_t st);
 void reduce_probe_launch(const float* x, float* out, hipStream_t st);
@@ -359,11 +365,12 @@ void ema_update_launch(float* ema, const float* w, long long n, const float* hyp
 void ema_swap_launch(float* w, float* ema, uint16_t* shadow, long long n, hipStream_t st);
 // ---- lamb.hip ----
 int lamb_chunk_elems();
-// p, g, m, v 16-byte aligned, shadow 8-byte aligned (checked by the binding); C chunks, T tensors
+// p, g, m, v 16-byte aligned, shadow 8-byte aligned (checked by the binding); C chunks, T tensors;
+// tgroup (T,) tensor → group with hyper of 8 + 4 G floats, or null: every tensor in group 0
 void lamb_launch(float* p, float* g, float* m, float* v, uint16_t* shadow, long long n, const float* hyper,
                  const long long* chunks, long long C, const int* tensors, const float* topt, int T, float* partials,
                  float* trust, float eps, float clip, float gscale, int zero_g, const float* loss_src,
-                 float* loss_ring, int ring_n, const float* norm_part, hipStream_t st);
+                 float* loss_ring, int ring_n, const float* norm_part, const int* tgroup, int G, hipStream_t st);
 // ---- mlm_head.hip ----
 void mlm_select_launch(const int64_t* labels, int B, int L, int cap, int gcap, int64_t* idx_b, int64_t* lab_b,
                        int* count, int64_t* gidx, int64_t* glab, float* total, bool* overflow, bool* sticky,

@@ -206,11 +206,23 @@ __global__ __launch_bounds__(256) void lamb_apply_kernel(float* __restrict__ p, 
                                                          long long n, const float* __restrict__ hyper,
                                                          const long long* __restrict__ chunks,
                                                          const float* __restrict__ topt, int T,
-                                                         const float* __restrict__ trust, float eps) {
-  const float lr = hyper[0], step = hyper[1], beta1 = hyper[3], beta2 = hyper[4];
+                                                         const float* __restrict__ trust, float eps,
+                                                         const int* __restrict__ tgroup, int G) {
+  const float step = hyper[1], beta1 = hyper[3], beta2 = hyper[4];
   const float bc1 = lamb_bias_correction(beta1, step), bc2s = sqrtf(lamb_bias_correction(beta2, step));
   const LambChunk c = lamb_chunk(chunks, n, T);
   if (!c.ok) return;
+  // the tensor's lr: its group's word behind the 8 global ones (hyper[8 + 4 j], the layout of
+  // adamw_grouped_kernel); without a group table every tensor takes group 0's, hyper[0]
+  float lr = hyper[0];
+  if (tgroup != nullptr) {
+    const int grp = tgroup[c.tid];
+    if (grp < 0 || grp >= G) {  // uniform over the block
+      if (threadIdx.x == 0) pio_flag(kErrOptTable);
+      return;
+    }
+    lr = hyper[8 + 4 * grp];
+  }
   const float wd = topt[2 * c.tid];
   const float a = -(lr * trust[c.tid]);
   const int len4 = c.len >> 2;
@@ -253,17 +265,18 @@ __global__ __launch_bounds__(256) void lamb_apply_kernel(float* __restrict__ p, 
 
 int lamb_chunk_elems() { return kLambChunk; }
 
-// p, g, m, v 16-byte aligned, shadow 8-byte aligned (checked by the binding); C chunks, T tensors
+// p, g, m, v 16-byte aligned, shadow 8-byte aligned (checked by the binding); C chunks, T tensors;
+// tgroup (T,) tensor → group with hyper of 8 + 4 G floats, or null: every tensor in group 0
 void lamb_launch(float* p, float* g, float* m, float* v, uint16_t* shadow, long long n, const float* hyper,
                  const long long* chunks, long long C, const int* tensors, const float* topt, int T, float* partials,
                  float* trust, float eps, float clip, float gscale, int zero_g, const float* loss_src,
-                 float* loss_ring, int ring_n, const float* norm_part, hipStream_t st) {
+                 float* loss_ring, int ring_n, const float* norm_part, const int* tgroup, int G, hipStream_t st) {
   if (C <= 0 || T <= 0) return;
   hipLaunchKernelGGL(lamb_moments_kernel, dim3((unsigned)C), dim3(256), 0, st, p, g, m, v, n, hyper, chunks, topt, T,
                      partials, eps, clip, gscale, zero_g, loss_src, loss_ring, ring_n, norm_part);
   hipLaunchKernelGGL(lamb_trust_kernel, dim3((unsigned)T), dim3(256), 0, st, partials, tensors, topt, C, trust);
   hipLaunchKernelGGL(lamb_apply_kernel, dim3((unsigned)C), dim3(256), 0, st, p, m, v, shadow, n, hyper, chunks, topt, T,
-                     trust, eps);
+                     trust, eps, tgroup, G);
 }
 
 }  // namespace pio

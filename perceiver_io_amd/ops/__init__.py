@@ -70,8 +70,10 @@ def check_device_errors(reset: bool = True) -> None:
     * checked builds (``PERCEIVER_CHECKED=1``): the index-validation words — token ids, gather
       rows and class labels outside their tables (the kernels clamped / skipped the access), and
       bit 16: a ``batch_augment`` crop box that reached outside its source image (clamped; the
-      call itself never raises for it), and bit 32: a ``rand_augment`` op word outside its table
-      (applied as identity).
+      call itself never raises for it), bit 32: a ``rand_augment`` op word outside its table
+      (applied as identity), and bit 64: a chunk of ``adamw_grouped`` outside the flat buffers, or
+      a group id of ``adamw_grouped`` / ``lamb(tensor_group=)`` outside the optimizer's groups (the
+      chunk is skipped; ``lamb`` skips a chunk outside the buffers without flagging it).
       Outside a graph capture every checked launch raises at once (``checked_sync``); inside a
       replayed hipGraph nothing can.
 
@@ -96,7 +98,8 @@ def check_device_errors(reset: bool = True) -> None:
                                "1 token id >= vocab, 2 gather row out of range, 4 label outside [0, V) and != -100, "
                                "8 PE row index outside the position-encoding table, "
                                "16 batch_augment crop box outside its source image, "
-                               "32 rand_augment op word outside its table)")
+                               "32 rand_augment op word outside its table, "
+                               "64 adamw_grouped chunk outside the flat buffers, or an optimizer group id outside its groups)")
 
 
 def use_hip(t: torch.Tensor) -> bool:

@@ -923,13 +923,67 @@ def adamw(p, g, m, v, shadow, hyper, eps, wd, clip, gscale, l2=False, zero_grad=
         shadow.copy_(p.to(shadow.dtype))
 
 
+def _tensor_ranges(chunk_tab):
+    """[(tensor, lo, hi)] of a chunk table (``ops.optim.lamb_tables``): a tensor's chunks are
+    consecutive and cover it exactly."""
+    out = []
+    for start, length, t in chunk_tab.tolist():
+        if out and out[-1][0] == t:
+            out[-1][2] += length
+        else:
+            out.append([t, start, start + length])
+    return out
+
+
+def adamw_grouped(p, g, m, v, shadow, hyper, chunk_tab, tensor_group, groups, clip, gscale, l2=False, zero_grad=False,
+                  loss_src=None, loss_ring=None, norm_part=None):
+    """AdamW with per-group lr / weight decay / eps, tensor by tensor (csrc/elementwise.hip
+    adamw_grouped_kernel): tensor ``t`` takes ``hyper[8 + 4j : 8 + 4j + 3]`` of its group
+    ``j = tensor_group[t]``; step, betas, the clip factor (the norm of all groups together),
+    ``gscale``, ``l2`` and ``zero_grad`` are those of :func:`adamw`.  Padding between tensors belongs
+    to no chunk and is left alone."""
+    step, b1, b2 = float(hyper[1]), float(hyper[3]), float(hyper[4])
+    if loss_src is not None:  # the step's loss into the engine's ring slot hyper[7]
+        loss_ring.view(-1)[int(float(hyper[7])) % loss_ring.numel()] = loss_src.reshape(())
+    gs = gscale
+    if clip > 0:
+        norm = math.sqrt(float(norm_part.sum())) * gscale  # norm of the mean (all-reduced sum × 1/world)
+        f = clip / (norm + 1e-6)
+        if f < 1:
+            gs *= f
+    bc1, bc2 = 1 - b1 ** step, 1 - b2 ** step
+    hv, tg = hyper.tolist(), tensor_group.tolist()
+    for t, lo, hi in _tensor_ranges(chunk_tab):
+        j = tg[t]
+        if not 0 <= j < groups:
+            raise ValueError(f"adamw_grouped: tensor {t} in group {j} of {groups}")
+        lr, wd, eps = hv[8 + 4 * j:8 + 4 * j + 3]
+        w, gt, mt, vt = p[lo:hi], g[lo:hi], m[lo:hi], v[lo:hi]
+        gg = gt * gs
+        if zero_grad:
+            gt.zero_()
+        if l2:
+            gg = gg + wd * w
+        else:
+            w.mul_(1 - lr * wd)
+        mt.mul_(b1).add_(gg, alpha=1 - b1)
+        vt.mul_(b2).addcmul_(gg, gg, value=1 - b2)
+        denom = (vt.sqrt() / math.sqrt(bc2)).add_(eps)
+        w.addcdiv_(mt, denom, value=-lr / bc1)
+        if shadow is not None:
+            shadow[lo:hi].copy_(w.to(shadow.dtype))
+
+
 def lamb(p, g, m, v, shadow, hyper, chunk_tab, tensor_tab, tensor_opt, partials, trust, eps, clip, gscale,
-         zero_grad=False, loss_src=None, loss_ring=None, norm_part=None):
+         zero_grad=False, loss_src=None, loss_ring=None, norm_part=None, tensor_group=None):
     """LAMB over the flat buffers, tensor by tensor (csrc/lamb.hip; the tables of
     ``ops.optim.lamb_tables``): u = m̂ / (sqrt(v̂) + eps) + wd·w, trust = ‖w‖ / ‖u‖ for adapted
     tensors with non-zero norms (else 1), w ← w − lr·trust·u.  Padding between tensors belongs to
-    no chunk and is left alone.  ``partials`` is the kernels' scratch: unused here."""
+    no chunk and is left alone.  ``partials`` is the kernels' scratch: unused here.
+    ``tensor_group`` (T,): tensor ``t`` takes its group's lr ``hyper[8 + 4·tensor_group[t]]``
+    (None: every tensor group 0's, ``hyper[0]``)."""
     lr, step, b1, b2 = float(hyper[0]), float(hyper[1]), float(hyper[3]), float(hyper[4])
+    lrs = None if tensor_group is None else [float(hyper[8 + 4 * j]) for j in tensor_group.tolist()]
     if loss_src is not None:  # the step's loss into the engine's ring slot hyper[7]
         loss_ring.view(-1)[int(float(hyper[7])) % loss_ring.numel()] = loss_src.reshape(())
     gs = gscale
@@ -955,7 +1009,7 @@ def lamb(p, g, m, v, shadow, hyper, chunk_tab, tensor_tab, tensor_opt, partials,
             nw, nu = torch.linalg.vector_norm(w.float()), torch.linalg.vector_norm(u.float())
             tr = torch.where((nw > 0) & (nu > 0), nw / nu, tr)
         trust[t] = tr
-        w.sub_(u * (lr * tr))
+        w.sub_(u * ((lr if lrs is None else lrs[t]) * tr))
         if shadow is not None:
             shadow[lo:hi].copy_(w.to(shadow.dtype))
 

@@ -20,6 +20,10 @@ such as ``OneCycleLR`` drive it through ``param_groups``) with torch.optim.AdamW
 and a torch-compatible ``state_dict`` layout (``exp_avg``/``exp_avg_sq``/``step`` per
 parameter), so Lightning-layout checkpoints round-trip.  lr/betas/step live in a small
 device tensor refreshed before each step, which keeps the update capturable in a hipGraph.
+With several parameter groups (at most 8; ``lr``, ``weight_decay`` and ``eps`` per group, equal
+``betas``) that tensor carries 4 more words per group and the update is ``adamw_grouped`` over
+the chunk table of the flat buffer; one group runs the single-group kernel as before.
+``param_groups`` builds the usual groups (no decay on 1-d tensors, a prefix → lr multiplier map).
 
 ``Lamb`` / ``FusedLamb`` add LAMB: the flat space knows where tensors begin (``offsets``), so the
 fused update takes per-tensor trust ratios and per-tensor weight decay from chunk tables
@@ -42,6 +46,7 @@ ALIGN = 64  # elements; keeps every parameter view 256-byte aligned
 
 
 GRAD_REPLICAS = 8  # matches kGradReplicas in csrc/rowgemm.hip
+MAX_GROUPS = 8  # parameter groups of a fused optimizer; matches kAdamMaxGroups in csrc/elementwise.hip
 
 
 class FlatParameterSpace:
@@ -172,23 +177,40 @@ class FusedAdamW(torch.optim.Optimizer):
         defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False,
                         maximize=False, foreach=None, capturable=False, differentiable=False, fused=None)
         super().__init__(params, defaults)
-        if len(self.param_groups) != 1:
-            raise ValueError("FusedAdamW supports a single parameter group")
+        G = len(self.param_groups)
+        if G > MAX_GROUPS:
+            raise ValueError(f"{type(self).__name__} supports at most {MAX_GROUPS} parameter groups, got {G}")
+        for g in self.param_groups[1:]:
+            if tuple(g["betas"]) != tuple(self.param_groups[0]["betas"]):
+                raise ValueError(f"{type(self).__name__}: betas must be equal in every parameter group "
+                                 f"(lr, weight_decay and eps are per group)")
         # always with the bf16 shadow the fused executor reads its GEMM operands from (also for the
         # CPU emulation: re-homed parameters do not share the flat buffer's version counter, so a
         # version-keyed weight cache would never see the in-place update)
-        self.flat = flat if flat is not None else FlatParameterSpace(self.param_groups[0]["params"], with_shadow=True)
+        # Without ``flat`` the buffer is laid out in group order.  A caller that needs another order (the
+        # Trainer keeps MODEL order, so the reducer's ready points stay contiguous ranges) passes its own
+        # space over the same parameters: groups need not be contiguous in it.
+        self.flat = flat if flat is not None else FlatParameterSpace(
+            [p for g in self.param_groups for p in g["params"]], with_shadow=True)
+        homed = {id(p) for p in self.flat.params}
+        if any(p.requires_grad and id(p) not in homed for g in self.param_groups for p in g["params"]):
+            raise ValueError(f"{type(self).__name__}: a trainable parameter of the groups is missing from `flat`")
         dev = self.flat.device
         self.exp_avg = torch.zeros(self.flat.numel, dtype=torch.float32, device=dev)
         self.exp_avg_sq = torch.zeros(self.flat.numel, dtype=torch.float32, device=dev)
-        self.hyper = torch.zeros(8, dtype=torch.float32, device=dev)
+        # 8 global words; with several groups 4 more per group (lr, weight decay, eps, reserved)
+        self.hyper = torch.zeros(8 if G == 1 else 8 + 4 * G, dtype=torch.float32, device=dev)
+        # several groups: the chunk table of the flat buffer and tensor → group (csrc adamw_grouped_kernel)
+        self.chunk_tab = self.tensor_group = None
+        if G > 1:
+            self.chunk_tab, self.tensor_group = group_tables(self.flat, self.param_groups)
         self.max_grad_norm = float(max_grad_norm)
         # the gradient's sum of squares as fixed-order per-block partials (sumsq → adamw norm_part):
         # no atomics, so the clip factor is bitwise reproducible in every mode
         self.norm_part = torch.zeros(512, dtype=torch.float32, device=dev) if self.max_grad_norm > 0 else None
         self.l2 = False  # decoupled decay (AdamW); FusedAdam sets the coupled L2 form
         self._step = 0
-        self._ring = _HostRing(8, 8, dev) if dev.type == "cuda" else None
+        self._ring = _HostRing(8, self.hyper.numel(), dev) if dev.type == "cuda" else None
         self.grad_scale = 1.0
         # bucket mode (set by the step engine with a data-parallel reducer): each gradient bucket
         # is updated by range_update right after its all-reduce lands, on the reducer's side
@@ -224,7 +246,11 @@ class FusedAdamW(torch.optim.Optimizer):
         if self.ema is not None and self.ema.swapped:
             raise RuntimeError("optimizer step while the averaged weights are swapped in (WeightEMA.swap)")
         omd = 0.0 if self.ema is None else self.ema.one_minus_decay(self._step + 1)
-        return [float(g["lr"]), float(self._step + 1), 0.0, float(b1), float(b2), omd, 0.0, float(self.loss_slot)]
+        vals = [float(g["lr"]), float(self._step + 1), 0.0, float(b1), float(b2), omd, 0.0, float(self.loss_slot)]
+        if len(self.param_groups) > 1:  # the group words: every group's scheduled lr reaches a replayed step
+            for g in self.param_groups:
+                vals += [float(g["lr"]), float(g["weight_decay"]), float(g["eps"]), 0.0]
+        return vals
 
     def stage_hyper(self):
         """Write lr / step / betas for the NEXT update into device memory (outside any graph)."""
@@ -237,14 +263,18 @@ class FusedAdamW(torch.optim.Optimizer):
     def bucket_updates_ok(self) -> bool:
         """Per-bucket updates are exact only without a global gradient norm (clipping), without
         replicated gradient accumulators (a later fold would add into an updated range) and without
-        a weight EMA (the side-stream updates would finish after its launch)."""
-        return self.max_grad_norm <= 0 and self.flat.grad_rep is None and self.ema is None
+        a weight EMA (the side-stream updates would finish after its launch); a range knows no
+        tensor boundaries, so several parameter groups take the whole-buffer update too."""
+        return (self.max_grad_norm <= 0 and self.flat.grad_rep is None and self.ema is None
+                and len(self.param_groups) == 1)
 
     def range_update(self, lo: int, hi: int):
         """Fused AdamW over flat elements [lo, hi) only (the same per-element arithmetic as the
         whole-buffer kernel, so a step made of range updates is bitwise the full update); the
         gradient range is cleared as it is consumed.  Reads the hyper-parameters already staged
         for this step."""
+        if len(self.param_groups) > 1:
+            raise NotImplementedError("range updates take one parameter group (a range knows no tensor boundaries)")
         K = ext.require() if self.flat.device.type == "cuda" else emulation
         g = self.param_groups[0]
         f = self.flat
@@ -265,6 +295,14 @@ class FusedAdamW(torch.optim.Optimizer):
         if self.max_grad_norm > 0:
             K.sumsq(self.flat.grad, self.norm_part)
         lo = self.loss_out
+        if len(self.param_groups) > 1:
+            K.adamw_grouped(self.flat.data, self.flat.grad, self.exp_avg, self.exp_avg_sq, self.flat.shadow, self.hyper,
+                            self.chunk_tab, self.tensor_group, len(self.param_groups), self.max_grad_norm,
+                            self.grad_scale, l2=self.l2, zero_grad=zero_grad and self.flat.grad_rep is None,
+                            loss_src=None if lo is None else lo[0], loss_ring=None if lo is None else lo[1],
+                            norm_part=self.norm_part)
+            self._ema_update(K)
+            return
         K.adamw(self.flat.data, self.flat.grad, self.exp_avg, self.exp_avg_sq, self.flat.shadow, self.hyper,
                 g["eps"], g["weight_decay"], self.max_grad_norm, self.grad_scale, l2=self.l2,
                 zero_grad=zero_grad and self.flat.grad_rep is None,
@@ -285,12 +323,23 @@ class FusedAdamW(torch.optim.Optimizer):
         self.flat.zero_grad()
 
     # -- torch-compatible state dict ------------------------------------------------------
+    def _state_index(self):
+        """state key → index into ``flat.params``.  One group: the flat order itself (the layout of
+        every checkpoint so far).  Several groups: torch's convention, parameters numbered in group
+        order as in ``param_groups[j]["params"]``, so the state loads into a ``torch.optim.AdamW`` built
+        with the same groups."""
+        if len(self.param_groups) == 1:
+            return {i: i for i in range(len(self.flat.params))}
+        pos = {id(p): i for i, p in enumerate(self.flat.params)}
+        ordered = [p for g in self.param_groups for p in g["params"]]
+        return {k: pos[id(p)] for k, p in enumerate(ordered) if id(p) in pos}
+
     def state_dict(self):
         sd = super().state_dict()
         state = {}
         ea, es = self.flat.views(self.exp_avg), self.flat.views(self.exp_avg_sq)
-        for i in range(len(self.flat.params)):
-            state[i] = {"step": torch.tensor(float(self._step)), "exp_avg": ea[i].clone(), "exp_avg_sq": es[i].clone()}
+        for k, i in self._state_index().items():
+            state[k] = {"step": torch.tensor(float(self._step)), "exp_avg": ea[i].clone(), "exp_avg_sq": es[i].clone()}
         sd["state"] = state
         return sd
 
@@ -303,8 +352,9 @@ class FusedAdamW(torch.optim.Optimizer):
                     g[k] = v
         ea, es = self.flat.views(self.exp_avg), self.flat.views(self.exp_avg_sq)
         step = 0
+        index = self._state_index()
         for i, st in state.items():
-            i = int(i)
+            i = index[int(i)]
             if "exp_avg" in st:
                 ea[i].copy_(st["exp_avg"])
                 es[i].copy_(st["exp_avg_sq"])
@@ -330,21 +380,79 @@ class FusedAdam(FusedAdamW):
 LAMB_CHUNK = 4096  # elements per chunk of the LAMB tables; matches kLambChunk in csrc/lamb.hip
 
 
+def _cut_chunks(offsets, numels):
+    """Every tensor range cut into chunks of at most ``LAMB_CHUNK`` elements → ``chunks`` [(start,
+    length, tensor)] and ``tensors`` [(first chunk, chunks)]."""
+    chunks, tensors = [], []
+    for t, (o, n) in enumerate(zip(offsets, numels)):
+        tensors.append((len(chunks), (n + LAMB_CHUNK - 1) // LAMB_CHUNK))
+        for s in range(0, n, LAMB_CHUNK):
+            chunks.append((o + s, min(LAMB_CHUNK, n - s), t))
+    return chunks, tensors
+
+
+def group_tables(flat: FlatParameterSpace, param_groups):
+    """The device tables of an update with several parameter groups over ``flat``: ``chunk_tab``
+    (C, 3) int64 = (start, length, tensor), cut as for :func:`lamb_tables`, and ``tensor_group`` (T,)
+    int32 = the group of every tensor of ``flat.params`` (groups need not be contiguous in the
+    buffer)."""
+    group_of = {id(p): j for j, g in enumerate(param_groups) for p in g["params"]}
+    missing = [i for i, p in enumerate(flat.params) if id(p) not in group_of]
+    if missing:
+        raise ValueError(f"{len(missing)} parameter(s) of the flat space belong to no parameter group")
+    chunks, _ = _cut_chunks(flat.offsets, [p.numel() for p in flat.params])
+    return (torch.tensor(chunks, dtype=torch.int64, device=flat.device).reshape(-1, 3),
+            torch.tensor([group_of[id(p)] for p in flat.params], dtype=torch.int32, device=flat.device))
+
+
 def lamb_tables(offsets, numels, weight_decays, adapts, device):
     """The device tables of the fused LAMB update (csrc/lamb.hip) for tensors at ``offsets`` of
     a flat buffer: every tensor range cut into chunks of at most ``LAMB_CHUNK`` elements (never
     across a tensor boundary; the padding between tensors belongs to no chunk).  Returns
     ``chunk_tab`` (C, 3) int64 = (start, length, tensor), ``tensor_tab`` (T, 2) int32 = (first
     chunk, chunks) and ``tensor_opt`` (T, 2) fp32 = (weight decay, adapt)."""
-    chunks, tensors = [], []
-    for t, (o, n) in enumerate(zip(offsets, numels)):
-        tensors.append((len(chunks), (n + LAMB_CHUNK - 1) // LAMB_CHUNK))
-        for s in range(0, n, LAMB_CHUNK):
-            chunks.append((o + s, min(LAMB_CHUNK, n - s), t))
+    chunks, tensors = _cut_chunks(offsets, numels)
     opts = [(float(wd), 1.0 if a else 0.0) for wd, a in zip(weight_decays, adapts)]
     return (torch.tensor(chunks, dtype=torch.int64, device=device).reshape(-1, 3),
             torch.tensor(tensors, dtype=torch.int32, device=device).reshape(-1, 2),
             torch.tensor(opts, dtype=torch.float32, device=device).reshape(-1, 2))
+
+
+def param_groups(module: torch.nn.Module, weight_decay: float, no_decay_1d: bool = False, lr_scales=None):
+    """The two standard parameter-group recipes over ``module.named_parameters()`` (trainable ones):
+    ``no_decay_1d`` puts tensors with ``ndim ≤ 1`` (biases, LayerNorm gains) into groups with
+    ``weight_decay = 0``; ``lr_scales`` maps a name prefix to a learning-rate multiplier
+    (``{"encoder.": 0.1}``; the first matching prefix counts, no match is 1.0).  Returns the non-empty
+    groups (1–4 with one prefix) as ``{"params", "weight_decay", "lr_scale"}`` dicts in order of first
+    appearance; the caller sets ``lr = base · lr_scale`` (:func:`scale_group_lrs`)."""
+    lr_scales = dict(lr_scales or {})
+    groups = {}
+    for name, p in module.named_parameters():
+        if not p.requires_grad:
+            continue
+        scale = next((float(s) for pre, s in lr_scales.items() if name.startswith(pre)), 1.0)
+        wd = 0.0 if no_decay_1d and p.dim() <= 1 else float(weight_decay)
+        groups.setdefault((scale, wd), {"params": [], "weight_decay": wd, "lr_scale": scale})["params"].append(p)
+    return list(groups.values())
+
+
+def scale_group_lrs(groups, lr: float):
+    """``lr = base · lr_scale`` in every group of :func:`param_groups` (in place) → ``groups``."""
+    for g in groups:
+        g["lr"] = float(lr) * float(g.get("lr_scale", 1.0))
+    return groups
+
+
+def scale_scheduler_init(init: dict, groups) -> dict:
+    """A scheduler's ``{class_path, init_args}`` for an optimizer whose ``groups`` carry ``lr_scale``:
+    a scalar ``max_lr`` (``OneCycleLR``) becomes the per-group list ``max_lr · lr_scale``.  Anything
+    else — no ``max_lr``, a list already, no scaled group — is returned unchanged."""
+    args = dict(init.get("init_args", {}) or {})
+    scales = [float(g.get("lr_scale", 1.0)) for g in groups]
+    if not isinstance(args.get("max_lr"), (int, float)) or all(s == 1.0 for s in scales):
+        return init
+    args["max_lr"] = [float(args["max_lr"]) * s for s in scales]
+    return {**init, "init_args": args}
 
 
 class Lamb(torch.optim.Optimizer):
@@ -408,7 +516,8 @@ class Lamb(torch.optim.Optimizer):
 
 
 class FusedLamb(FusedAdamW):
-    """:class:`Lamb` over a :class:`FlatParameterSpace` (one parameter group): two streaming HIP
+    """:class:`Lamb` over a :class:`FlatParameterSpace` (up to 8 parameter groups with their own
+    ``lr``, ``weight_decay`` and ``exclude_1d``; ``betas`` and ``eps`` must be equal in every group): two streaming HIP
     kernels and a per-tensor reduction over chunk tables of the flat buffer (csrc/lamb.hip), or
     their emulation on the CPU.  A ``FusedAdamW`` to the step engine (captured update, loss ring,
     gradient cleared as it is consumed, ``grad_scale``), with an AdamW-layout ``state_dict``.  The
@@ -418,7 +527,12 @@ class FusedLamb(FusedAdamW):
                  exclude_1d: bool = True, max_grad_norm: float = 0.0, flat: Optional[FlatParameterSpace] = None):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
                          flat=flat)
-        self.param_groups[0]["exclude_1d"] = bool(exclude_1d)
+        for g in self.param_groups:  # a group option, as in Lamb
+            g.setdefault("exclude_1d", bool(exclude_1d))
+            # the LAMB kernels take one eps: refuse what plain Lamb would honour per group
+            if float(g["eps"]) != float(self.param_groups[0]["eps"]):
+                raise ValueError("FusedLamb: eps must be equal in every parameter group "
+                                 "(lr, weight_decay and exclude_1d are per group)")
         f = self.flat
         wds, adapts = self._tensor_options()
         self.chunk_tab, self.tensor_tab, self.tensor_opt = lamb_tables(
@@ -428,9 +542,11 @@ class FusedLamb(FusedAdamW):
         self.trust = torch.ones(len(f.params), dtype=torch.float32, device=f.device)
 
     def _tensor_options(self):
-        g = self.param_groups[0]
-        plain = [g["exclude_1d"] and p.dim() <= 1 for p in self.flat.params]
-        return [0.0 if pl else g["weight_decay"] for pl in plain], [not pl for pl in plain]
+        """Per tensor of ``flat.params``, from its group: (weight decay, adapt)."""
+        group_of = {id(p): g for g in self.param_groups for p in g["params"]}
+        groups = [group_of[id(p)] for p in self.flat.params]
+        plain = [g["exclude_1d"] and p.dim() <= 1 for g, p in zip(groups, self.flat.params)]
+        return [0.0 if pl else g["weight_decay"] for g, pl in zip(groups, plain)], [not pl for pl in plain]
 
     def last_trust(self) -> torch.Tensor:
         """(T,) fp32: the trust ratio every tensor of ``flat.params`` took in the last update."""
@@ -454,7 +570,7 @@ class FusedLamb(FusedAdamW):
                self.tensor_opt, self.partials, self.trust, self.param_groups[0]["eps"], self.max_grad_norm,
                self.grad_scale, zero_grad=zero_grad and f.grad_rep is None,
                loss_src=None if lo is None else lo[0], loss_ring=None if lo is None else lo[1],
-               norm_part=self.norm_part)
+               norm_part=self.norm_part, tensor_group=self.tensor_group)
         self._ema_update(K)
 
     def load_state_dict(self, state_dict):

@@ -18,6 +18,7 @@ selected positions); ``step`` on the ``reference`` backend reproduces the full-l
 """
 from __future__ import annotations
 
+import inspect
 import os
 import warnings
 from typing import Any, List, Optional, Tuple
@@ -27,7 +28,7 @@ import torch.nn as nn
 
 from .models import (ClassificationOutputAdapter, ImageInputAdapter, PerceiverDecoder, PerceiverEncoder, PerceiverIO,
                      PerceiverMLM, TextInputAdapter, TextMasking, TextOutputAdapter)
-from .train.module import LitModuleBase, instantiate_class
+from .train.module import LitModuleBase, import_class, instantiate_class
 from .utils.misc import freeze, predict_masked_samples
 from .utils.tokenizer import MASK_TOKEN_ID, PAD_TOKEN_ID, SPECIAL_TOKENS, UNK_TOKEN_ID
 
@@ -67,7 +68,9 @@ class LitModel(LitModuleBase):
                  num_encoder_self_attention_heads: int = 4,
                  num_encoder_self_attention_layers_per_block: int = 6,
                  num_decoder_cross_attention_heads: int = 4,
-                 dropout: float = 0.0):
+                 dropout: float = 0.0,
+                 no_decay_1d: bool = False,
+                 encoder_lr_scale: float = 1.0):
         super().__init__()
         self.save_hyperparameters()
 
@@ -75,7 +78,43 @@ class LitModel(LitModuleBase):
     def latent_shape(self) -> Tuple[int, int]:
         return self.hparams.num_latents, self.hparams.num_latent_channels
 
+    def optimizer_groups(self):
+        """The parameter groups of ``no_decay_1d`` / ``encoder_lr_scale`` (``ops.optim.param_groups``
+        over ``self.model``, ``lr = optimizer lr · lr_scale`` per group), or None with the defaults
+        (checkpoints from before the two options lack them: the defaults)."""
+        no_decay = bool(self.hparams.get("no_decay_1d", False))
+        scale = self.hparams.get("encoder_lr_scale", 1.0)
+        scale = 1.0 if scale is None else float(scale)  # 0 is a value: the encoder stands still
+        if not no_decay and scale == 1.0:
+            return None
+        from .ops.optim import param_groups, scale_group_lrs
+
+        init = self.hparams.optimizer_init
+        cls_defaults = inspect.signature(import_class(init["class_path"]).__init__).parameters
+        args = dict(init.get("init_args", {}) or {})
+        lr = args.get("lr", cls_defaults["lr"].default)
+        wd = args.get("weight_decay", cls_defaults["weight_decay"].default)
+        enc = getattr(self.model, "encoder", None)
+        prefix = next((n + "." for n, m in self.model.named_children() if m is enc), None)
+        scales = {prefix: scale} if prefix is not None and scale != 1.0 else None
+        groups = param_groups(self.model, wd, no_decay_1d=no_decay, lr_scales=scales)
+        seen = {id(p) for g in groups for p in g["params"]}
+        rest = [p for p in self.parameters() if p.requires_grad and id(p) not in seen]
+        if rest:  # parameters outside self.model: plain options
+            groups.append({"params": rest, "weight_decay": float(wd), "lr_scale": 1.0})
+        return scale_group_lrs(groups, lr)
+
     def configure_optimizers(self):
+        groups = self.optimizer_groups()
+        if groups is not None:
+            from .ops.optim import scale_scheduler_init
+
+            optimizer = instantiate_class(groups, self.hparams.optimizer_init)
+            if self.hparams.get("scheduler_init") is None:
+                return optimizer
+            scheduler = instantiate_class(optimizer, scale_scheduler_init(self.hparams.scheduler_init, groups))
+            return {"optimizer": optimizer,
+                    "lr_scheduler": {"scheduler": scheduler, "interval": "step", "frequency": 1}}
         optimizer = instantiate_class(self.parameters(), self.hparams.optimizer_init)
         if self.hparams.get("scheduler_init") is None:
             return optimizer

@@ -238,9 +238,10 @@ class StepEngine:
             self.opt.step(staged=self.bucket_update)
         else:
             if self.reducer is not None and self.reducer.enabled:
-                for p in self.opt.param_groups[0]["params"]:
-                    if p.grad is not None:
-                        p.grad.mul_(self.reducer.grad_scale())
+                for g in self.opt.param_groups:
+                    for p in g["params"]:
+                        if p.grad is not None:
+                            p.grad.mul_(self.reducer.grad_scale())
             self.opt.step()
             if self.ema is not None:
                 self._plain_steps += 1

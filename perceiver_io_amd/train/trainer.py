@@ -273,41 +273,44 @@ class Trainer:
                 sched = s["scheduler"] if isinstance(s, dict) else s
         else:
             opt = res
-        if self.fused and type(opt).__name__ in ("AdamW", "Adam"):
-            from ..ops.optim import FusedAdamW
+        kind = type(opt).__name__
+        if self.fused and kind in ("AdamW", "Adam", "Lamb"):
+            from ..ops.optim import FlatParameterSpace, FusedAdamW, FusedLamb, scale_scheduler_init
 
-            g = opt.param_groups[0]
-            wd = g.get("weight_decay", 0.0)
-            if type(opt).__name__ == "Adam" and wd:
-                warnings.warn("Adam with L2 weight decay is executed as decoupled AdamW by the fused optimizer")
-            new = FusedAdamW([p for p in model.parameters() if p.requires_grad], lr=g["lr"], betas=g["betas"],
-                             eps=g["eps"], weight_decay=wd, max_grad_norm=self.gradient_clip_val)
+            # the same groups as the optimizer it replaces: trainable parameters only, empty groups dropped
+            keys = ("lr", "betas", "eps", "weight_decay", "lr_scale") + (("exclude_1d",) if kind == "Lamb" else ())
+            groups = []
+            for g in opt.param_groups:
+                ps = [p for p in g["params"] if p.requires_grad]
+                if ps:
+                    groups.append({"params": ps, **{k: g[k] for k in keys if k in g}})
+            if not groups:
+                raise ValueError("no trainable parameters")
+            g = groups[0]
+            # the flat buffer keeps MODEL order whatever the groups (they need not be contiguous in it):
+            # the reducer's ready points (decoder, layer_n) stay contiguous index ranges, as with one group
+            grouped = {id(p) for gr in groups for p in gr["params"]}
+            ordered = [p for p in model.parameters() if id(p) in grouped]
+            seen = {id(p) for p in ordered}
+            ordered += [p for gr in groups for p in gr["params"] if id(p) not in seen]
+            flat = FlatParameterSpace(ordered, with_shadow=True)
+            if kind == "Lamb":
+                new = FusedLamb(groups, lr=g["lr"], betas=g["betas"], eps=g["eps"],
+                                weight_decay=g.get("weight_decay", 0.0), exclude_1d=g.get("exclude_1d", True),
+                                max_grad_norm=self.gradient_clip_val or getattr(opt, "max_grad_norm", 0.0), flat=flat)
+            else:
+                if kind == "Adam" and any(g.get("weight_decay", 0.0) for g in groups):
+                    warnings.warn("Adam with L2 weight decay is executed as decoupled AdamW by the fused optimizer")
+                new = FusedAdamW(groups, lr=g["lr"], betas=g["betas"], eps=g["eps"],
+                                 weight_decay=g.get("weight_decay", 0.0), max_grad_norm=self.gradient_clip_val,
+                                 flat=flat)
             if sched is not None:
                 init = getattr(model.hparams, "get", lambda *_: None)("scheduler_init")
                 if init is not None:
                     from .module import instantiate_class
 
-                    sched = instantiate_class(new, init)
-                else:
-                    warnings.warn("scheduler could not be re-bound to the fused optimizer; dropped")
-                    sched = None
-            opt = new
-        elif self.fused and type(opt).__name__ == "Lamb":
-            from ..ops.optim import FusedLamb
-
-            g = opt.param_groups[0]
-            if len(opt.param_groups) > 1:
-                warnings.warn("the fused LAMB takes the first parameter group's options for every parameter")
-            new = FusedLamb([p for p in model.parameters() if p.requires_grad], lr=g["lr"], betas=g["betas"],
-                            eps=g["eps"], weight_decay=g.get("weight_decay", 0.0),
-                            exclude_1d=g.get("exclude_1d", True),
-                            max_grad_norm=self.gradient_clip_val or getattr(opt, "max_grad_norm", 0.0))
-            if sched is not None:
-                init = getattr(model.hparams, "get", lambda *_: None)("scheduler_init")
-                if init is not None:
-                    from .module import instantiate_class
-
-                    sched = instantiate_class(new, init)
+                    # a scalar max_lr follows the groups' lr_scale, as in configure_optimizers
+                    sched = instantiate_class(new, scale_scheduler_init(init, new.param_groups))
                 else:
                     warnings.warn("scheduler could not be re-bound to the fused optimizer; dropped")
                     sched = None
