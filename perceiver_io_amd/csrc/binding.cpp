@@ -24,8 +24,8 @@ hipStream_t stream() { return at::hip::getCurrentHIPStream(); }
 // outside [0, V) ∪ {-100}, 8: a PE row index outside its table, 16: a batch_augment crop box that had to be
 // clamped into its source image, 32: a rand_augment op word outside its table); reset clears them
 int64_t check_errors(bool reset) {
-  return (int64_t)(pio::check_errors_elementwise(reset) | pio::check_errors_mlm_head(reset) |
-                   pio::check_errors_ce_head(reset) | pio::check_errors_topk_head(reset) |
+  return (int64_t)(pio::check_errors_elementwise(reset) | pio::check_errors_optim(reset) |
+                   pio::check_errors_mlm_head(reset) | pio::check_errors_ce_head(reset) | pio::check_errors_topk_head(reset) |
                    pio::check_errors_rowgemm(reset) | pio::check_errors_pixel_head(reset) |
                    pio::check_errors_soft_ce_head(reset) | pio::check_errors_augment(reset) |
                    pio::check_errors_randaugment(reset));
@@ -1835,27 +1835,88 @@ std::vector<Tensor> nonzero_compact(Tensor img, int64_t cap, int64_t segs, int64
   return {values, index, kmask, count};
 }
 
+// ---- the flat-space optimizers (csrc/optim.hip, lamb.hip, ema.hip): one set of argument checks ----
+namespace {
+bool aligned(const void* q, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(q) & (bytes - 1)) == 0; }
+
+// p, g, m, v: contiguous fp32 device buffers of one size; shadow (optional): contiguous bf16 of that
+// size; hyper: contiguous fp32 of at least 8 words on the device.  need_vec: the kernels take float4 /
+// uint2 accesses only (adamw falls back to its scalar kernel instead)
+struct FlatBufs {
+  float *p, *g, *m, *v;
+  uint16_t* shadow;
+  long long n;
+  const float* hyper;
+};
+FlatBufs flat_bufs(const char* fn, const Tensor& p, const Tensor& g, const Tensor& m, const Tensor& v,
+                   const OptT& shadow, const Tensor& hyper, bool need_vec) {
+  for (const Tensor* t : {&p, &g, &m, &v, &hyper})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kFloat32 && t->is_contiguous(), fn,
+                ": p, g, m, v and hyper must be contiguous fp32 GPU tensors");
+  TORCH_CHECK(p.numel() == g.numel() && p.numel() == m.numel() && p.numel() == v.numel(), fn,
+              ": p, g, m, v must have one size");
+  TORCH_CHECK(hyper.numel() >= 8, fn, ": hyper of at least 8 floats");
+  FlatBufs b{p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), nullptr, p.numel(),
+             hyper.data_ptr<float>()};
+  if (shadow.has_value()) {
+    TORCH_CHECK(shadow->is_cuda() && shadow->scalar_type() == torch::kBFloat16 && shadow->is_contiguous() &&
+                    shadow->numel() == p.numel(),
+                fn, ": shadow must be a contiguous bf16 GPU tensor of p's size");
+    b.shadow = reinterpret_cast<uint16_t*>(shadow->data_ptr());
+  }
+  TORCH_CHECK(!need_vec || (aligned(b.p, 16) && aligned(b.g, 16) && aligned(b.m, 16) && aligned(b.v, 16) &&
+                            aligned(b.shadow, 8)),
+              fn, ": the flat buffers must be 16-byte aligned (the shadow 8-byte)");
+  return b;
+}
+
+// the step's loss → loss_ring[hyper[7] % n]: both or neither
+struct LossRing {
+  const float* src;
+  float* ring;
+  int n;
+};
+LossRing loss_ring_args(const char* fn, const OptT& loss_src, const OptT& loss_ring) {
+  TORCH_CHECK(loss_src.has_value() == loss_ring.has_value(), fn, ": loss_src and loss_ring go together");
+  if (!loss_src.has_value()) return {nullptr, nullptr, 1};
+  CHECK_DT(*loss_src, torch::kFloat32); CHECK_DT(*loss_ring, torch::kFloat32);
+  TORCH_CHECK(loss_src->numel() == 1 && loss_ring->is_contiguous() && loss_ring->numel() >= 1, fn,
+              ": scalar loss_src, contiguous loss_ring, hyper[7] = ring slot");
+  return {loss_src->data_ptr<float>(), loss_ring->data_ptr<float>(), (int)loss_ring->numel()};
+}
+
+// the gradient's sumsq partials, needed (and read) only when clipping
+const float* norm_part_arg(const char* fn, double clip, const OptT& norm_part) {
+  if (clip <= 0) return nullptr;
+  TORCH_CHECK(norm_part.has_value() && norm_part->is_contiguous() && norm_part->numel() >= kSumsqParts &&
+                  norm_part->scalar_type() == torch::kFloat32,
+              fn, ": clip > 0 needs norm_part (the sumsq partials of the gradient)");
+  return norm_part->data_ptr<float>();
+}
+
+// chunk_tab (C, 3) int64 = (start, length, tensor) → its pointer; C fits an int
+const long long* chunk_tab_arg(const char* fn, const Tensor& chunk_tab) {
+  TORCH_CHECK(chunk_tab.is_cuda() && chunk_tab.scalar_type() == torch::kInt64 && chunk_tab.dim() == 2 &&
+                  chunk_tab.size(1) == 3 && chunk_tab.is_contiguous() && chunk_tab.size(0) < (int64_t(1) << 31),
+              fn, ": chunk_tab must be a contiguous (C, 3) int64 GPU tensor");
+  return reinterpret_cast<const long long*>(chunk_tab.data_ptr<int64_t>());
+}
+
+// tensor_group (T,) int32 = tensor → group
+const int* tensor_group_arg(const char* fn, const Tensor& tensor_group, int64_t T) {
+  TORCH_CHECK(tensor_group.is_cuda() && tensor_group.scalar_type() == torch::kInt32 && tensor_group.is_contiguous() &&
+                  tensor_group.numel() == T && T < (int64_t(1) << 31),
+              fn, ": tensor_group must be a contiguous (T,) int32 GPU tensor");
+  return tensor_group.data_ptr<int>();
+}
+}  // namespace
+
 void adamw(Tensor p, Tensor g, Tensor m, Tensor v, OptT shadow, Tensor hyper, double eps, double wd, double clip,
            double gscale, bool l2, bool zero_grad, OptT loss_src, OptT loss_ring, OptT norm_part) {
-  TORCH_CHECK(clip <= 0 || (norm_part.has_value() && norm_part->is_contiguous() && norm_part->numel() >= kSumsqParts &&
-                            norm_part->scalar_type() == torch::kFloat32),
-              "adamw: clip > 0 needs norm_part (the sumsq partials of the gradient)");
-  TORCH_CHECK(p.is_contiguous() && g.is_contiguous() && m.is_contiguous() && v.is_contiguous());
-  TORCH_CHECK(p.numel() == g.numel() && p.numel() == m.numel() && p.numel() == v.numel());
-  uint16_t* sp = nullptr;
-  if (shadow.has_value()) { TORCH_CHECK(shadow->numel() == p.numel()); sp = reinterpret_cast<uint16_t*>(shadow->data_ptr()); }
-  TORCH_CHECK(loss_src.has_value() == loss_ring.has_value(), "adamw: loss_src and loss_ring go together");
-  if (loss_src.has_value()) {
-    CHECK_DT(*loss_src, torch::kFloat32); CHECK_DT(*loss_ring, torch::kFloat32);
-    TORCH_CHECK(loss_src->numel() == 1 && loss_ring->is_contiguous() && loss_ring->numel() >= 1 && hyper.numel() >= 8,
-                "adamw: scalar loss_src, contiguous loss_ring, hyper[7] = ring slot");
-  }
-  pio::adamw_launch(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), sp, p.numel(),
-                    f32p(hyper), (float)eps, (float)wd, (float)clip, (float)gscale, l2 ? 1 : 0, zero_grad ? 1 : 0,
-                    loss_src.has_value() ? f32p(*loss_src) : nullptr,
-                    loss_ring.has_value() ? loss_ring->data_ptr<float>() : nullptr,
-                    loss_ring.has_value() ? (int)loss_ring->numel() : 1,
-                    clip > 0 ? f32p(*norm_part) : nullptr, stream());
+  const FlatBufs b = flat_bufs("adamw", p, g, m, v, shadow, hyper, false);
+  const LossRing lr = loss_ring_args("adamw", loss_src, loss_ring);
+  pio::adamw_launch(b.p, b.g, b.m, b.v, b.shadow, b.n, b.hyper, (float)eps, (float)wd, (float)clip, (float)gscale,
+                    l2 ? 1 : 0, zero_grad ? 1 : 0, lr.src, lr.ring, lr.n, norm_part_arg("adamw", clip, norm_part), stream());
 }
 
 // fused LAMB over the flat buffers (csrc/lamb.hip): chunk_tab (C, 3) int64 = (start, length, tensor),
@@ -1864,105 +1925,48 @@ void adamw(Tensor p, Tensor g, Tensor m, Tensor v, OptT shadow, Tensor hyper, do
 void lamb(Tensor p, Tensor g, Tensor m, Tensor v, OptT shadow, Tensor hyper, Tensor chunk_tab, Tensor tensor_tab,
           Tensor tensor_opt, Tensor partials, Tensor trust, double eps, double clip, double gscale, bool zero_grad,
           OptT loss_src, OptT loss_ring, OptT norm_part, OptT tensor_group) {
-  TORCH_CHECK(clip <= 0 || (norm_part.has_value() && norm_part->is_contiguous() && norm_part->numel() >= kSumsqParts &&
-                            norm_part->scalar_type() == torch::kFloat32),
-              "lamb: clip > 0 needs norm_part (the sumsq partials of the gradient)");
-  CHECK_CUDA(p); CHECK_CUDA(g); CHECK_CUDA(m); CHECK_CUDA(v); CHECK_CUDA(hyper); CHECK_CUDA(chunk_tab);
+  const FlatBufs b = flat_bufs("lamb", p, g, m, v, shadow, hyper, true);
+  const LossRing lr = loss_ring_args("lamb", loss_src, loss_ring);
+  const long long* chunks = chunk_tab_arg("lamb", chunk_tab);
   CHECK_CUDA(tensor_tab); CHECK_CUDA(tensor_opt); CHECK_CUDA(partials); CHECK_CUDA(trust);
-  CHECK_DT(p, torch::kFloat32); CHECK_DT(g, torch::kFloat32); CHECK_DT(m, torch::kFloat32); CHECK_DT(v, torch::kFloat32);
-  TORCH_CHECK(p.is_contiguous() && g.is_contiguous() && m.is_contiguous() && v.is_contiguous());
-  TORCH_CHECK(p.numel() == g.numel() && p.numel() == m.numel() && p.numel() == v.numel());
-  uint16_t* sp = nullptr;
-  if (shadow.has_value()) {
-    CHECK_DT(*shadow, torch::kBFloat16);
-    TORCH_CHECK(shadow->is_contiguous() && shadow->numel() == p.numel());
-    sp = reinterpret_cast<uint16_t*>(shadow->data_ptr());
-  }
-  TORCH_CHECK(((reinterpret_cast<uintptr_t>(p.data_ptr()) | reinterpret_cast<uintptr_t>(g.data_ptr()) |
-                reinterpret_cast<uintptr_t>(m.data_ptr()) | reinterpret_cast<uintptr_t>(v.data_ptr())) & 15) == 0 &&
-                  (reinterpret_cast<uintptr_t>(sp) & 7) == 0,
-              "lamb: the flat buffers must be 16-byte aligned (the shadow 8-byte)");
-  CHECK_DT(chunk_tab, torch::kInt64); CHECK_DT(tensor_tab, torch::kInt32); CHECK_DT(tensor_opt, torch::kFloat32);
+  CHECK_DT(tensor_tab, torch::kInt32); CHECK_DT(tensor_opt, torch::kFloat32);
   CHECK_DT(partials, torch::kFloat32); CHECK_DT(trust, torch::kFloat32);
   const int64_t C = chunk_tab.size(0), T = tensor_tab.size(0);
-  TORCH_CHECK(chunk_tab.dim() == 2 && chunk_tab.size(1) == 3 && chunk_tab.is_contiguous() && tensor_tab.dim() == 2 &&
-                  tensor_tab.size(1) == 2 && tensor_tab.is_contiguous() && tensor_opt.is_contiguous() &&
-                  tensor_opt.dim() == 2 && tensor_opt.size(0) == T && tensor_opt.size(1) == 2,
-              "lamb: chunk_tab (C, 3) int64, tensor_tab (T, 2) int32, tensor_opt (T, 2) fp32, contiguous");
-  TORCH_CHECK(partials.is_contiguous() && partials.numel() >= 2 * C && trust.is_contiguous() && trust.numel() >= T &&
-                  hyper.numel() >= 8 && C < (int64_t(1) << 31) && T < (int64_t(1) << 31),
-              "lamb: partials >= 2 C floats, trust >= T floats, hyper of 8 floats");
-  TORCH_CHECK(loss_src.has_value() == loss_ring.has_value(), "lamb: loss_src and loss_ring go together");
-  if (loss_src.has_value()) {
-    CHECK_DT(*loss_src, torch::kFloat32); CHECK_DT(*loss_ring, torch::kFloat32);
-    TORCH_CHECK(loss_src->numel() == 1 && loss_ring->is_contiguous() && loss_ring->numel() >= 1,
-                "lamb: scalar loss_src, contiguous loss_ring, hyper[7] = ring slot");
-  }
+  TORCH_CHECK(tensor_tab.dim() == 2 && tensor_tab.size(1) == 2 && tensor_tab.is_contiguous() &&
+                  tensor_opt.is_contiguous() && tensor_opt.dim() == 2 && tensor_opt.size(0) == T &&
+                  tensor_opt.size(1) == 2 && T < (int64_t(1) << 31),
+              "lamb: tensor_tab (T, 2) int32, tensor_opt (T, 2) fp32, contiguous");
+  TORCH_CHECK(partials.is_contiguous() && partials.numel() >= 2 * C && trust.is_contiguous() && trust.numel() >= T,
+              "lamb: partials >= 2 C floats, trust >= T floats");
   // per-tensor lr: tensor_group (T,) int32 picks hyper[8 + 4 j]; the group count follows from hyper's width
   const int* tg = nullptr;
   int G = 1;
   if (tensor_group.has_value()) {
-    CHECK_CUDA(*tensor_group); CHECK_DT(*tensor_group, torch::kInt32);
+    tg = tensor_group_arg("lamb", *tensor_group, T);
     G = (int)((hyper.numel() - 8) / 4);
-    TORCH_CHECK(tensor_group->is_contiguous() && tensor_group->numel() == T && hyper.is_contiguous() && G >= 1 && G <= 8,
-                "lamb: tensor_group (T,) int32 with hyper of 8 + 4 G floats, 1 <= G <= 8");
-    tg = tensor_group->data_ptr<int>();
+    TORCH_CHECK(G >= 1 && G <= 8, "lamb: tensor_group needs hyper of 8 + 4 G floats, 1 <= G <= 8");
   }
-  pio::lamb_launch(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), sp, p.numel(),
-                   f32p(hyper), reinterpret_cast<const long long*>(chunk_tab.data_ptr<int64_t>()), C,
-                   tensor_tab.data_ptr<int>(), f32p(tensor_opt), (int)T, partials.data_ptr<float>(),
-                   trust.data_ptr<float>(), (float)eps, (float)clip, (float)gscale, zero_grad ? 1 : 0,
-                   loss_src.has_value() ? f32p(*loss_src) : nullptr,
-                   loss_ring.has_value() ? loss_ring->data_ptr<float>() : nullptr,
-                   loss_ring.has_value() ? (int)loss_ring->numel() : 1,
-                   clip > 0 ? f32p(*norm_part) : nullptr, tg, G, stream());
+  pio::lamb_launch(b.p, b.g, b.m, b.v, b.shadow, b.n, b.hyper, chunks, C, tensor_tab.data_ptr<int>(), f32p(tensor_opt),
+                   (int)T, partials.data_ptr<float>(), trust.data_ptr<float>(), (float)eps, (float)clip, (float)gscale,
+                   zero_grad ? 1 : 0, lr.src, lr.ring, lr.n, norm_part_arg("lamb", clip, norm_part), tg, G, stream());
 }
 
-// AdamW with per-group lr / weight decay / eps (elementwise.hip adamw_grouped_kernel): chunk_tab (C, 3)
+// AdamW with per-group lr / weight decay / eps (optim.hip adamw_grouped_kernel): chunk_tab (C, 3)
 // int64 = (start, length, tensor) as for lamb, tensor_group (T,) int32, hyper = 8 global words + 4 per
 // group (lr, weight decay, eps, reserved)
 void adamw_grouped(Tensor p, Tensor g, Tensor m, Tensor v, OptT shadow, Tensor hyper, Tensor chunk_tab,
                    Tensor tensor_group, int64_t groups, double clip, double gscale, bool l2, bool zero_grad, OptT loss_src,
                    OptT loss_ring, OptT norm_part) {
-  TORCH_CHECK(clip <= 0 || (norm_part.has_value() && norm_part->is_contiguous() && norm_part->numel() >= kSumsqParts &&
-                            norm_part->scalar_type() == torch::kFloat32),
-              "adamw_grouped: clip > 0 needs norm_part (the sumsq partials of the gradient)");
-  CHECK_CUDA(p); CHECK_CUDA(g); CHECK_CUDA(m); CHECK_CUDA(v); CHECK_CUDA(hyper); CHECK_CUDA(chunk_tab);
-  CHECK_CUDA(tensor_group);
-  CHECK_DT(p, torch::kFloat32); CHECK_DT(g, torch::kFloat32); CHECK_DT(m, torch::kFloat32); CHECK_DT(v, torch::kFloat32);
-  CHECK_DT(hyper, torch::kFloat32); CHECK_DT(chunk_tab, torch::kInt64); CHECK_DT(tensor_group, torch::kInt32);
-  TORCH_CHECK(p.is_contiguous() && g.is_contiguous() && m.is_contiguous() && v.is_contiguous());
-  TORCH_CHECK(p.numel() == g.numel() && p.numel() == m.numel() && p.numel() == v.numel());
-  uint16_t* sp = nullptr;
-  if (shadow.has_value()) {
-    CHECK_DT(*shadow, torch::kBFloat16);
-    TORCH_CHECK(shadow->is_contiguous() && shadow->numel() == p.numel());
-    sp = reinterpret_cast<uint16_t*>(shadow->data_ptr());
-  }
-  TORCH_CHECK(((reinterpret_cast<uintptr_t>(p.data_ptr()) | reinterpret_cast<uintptr_t>(g.data_ptr()) |
-                reinterpret_cast<uintptr_t>(m.data_ptr()) | reinterpret_cast<uintptr_t>(v.data_ptr())) & 15) == 0 &&
-                  (reinterpret_cast<uintptr_t>(sp) & 7) == 0,
-              "adamw_grouped: the flat buffers must be 16-byte aligned (the shadow 8-byte)");
-  const int64_t C = chunk_tab.size(0), T = tensor_group.numel();
-  TORCH_CHECK(chunk_tab.dim() == 2 && chunk_tab.size(1) == 3 && chunk_tab.is_contiguous() && tensor_group.is_contiguous() &&
-                  C < (int64_t(1) << 31) && T < (int64_t(1) << 31),
-              "adamw_grouped: chunk_tab (C, 3) int64, tensor_group (T,) int32, contiguous");
-  TORCH_CHECK(groups >= 1 && groups <= 8 && hyper.is_contiguous() && hyper.numel() >= 8 + 4 * groups,
+  const FlatBufs b = flat_bufs("adamw_grouped", p, g, m, v, shadow, hyper, true);
+  const LossRing lr = loss_ring_args("adamw_grouped", loss_src, loss_ring);
+  const long long* chunks = chunk_tab_arg("adamw_grouped", chunk_tab);
+  const int64_t T = tensor_group.numel();
+  const int* tg = tensor_group_arg("adamw_grouped", tensor_group, T);
+  TORCH_CHECK(groups >= 1 && groups <= 8 && hyper.numel() >= 8 + 4 * groups,
               "adamw_grouped: 1 <= groups <= 8 and hyper of 8 + 4 * groups floats");
-  TORCH_CHECK(loss_src.has_value() == loss_ring.has_value(), "adamw_grouped: loss_src and loss_ring go together");
-  if (loss_src.has_value()) {
-    CHECK_DT(*loss_src, torch::kFloat32); CHECK_DT(*loss_ring, torch::kFloat32);
-    TORCH_CHECK(loss_src->numel() == 1 && loss_ring->is_contiguous() && loss_ring->numel() >= 1,
-                "adamw_grouped: scalar loss_src, contiguous loss_ring, hyper[7] = ring slot");
-  }
-  TORCH_CHECK(pio::adamw_grouped_launch(
-                  p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), sp, p.numel(),
-                  f32p(hyper), reinterpret_cast<const long long*>(chunk_tab.data_ptr<int64_t>()), C,
-                  tensor_group.data_ptr<int>(), (int)T, (int)groups, (float)clip, (float)gscale, l2 ? 1 : 0,
-                  zero_grad ? 1 : 0, loss_src.has_value() ? f32p(*loss_src) : nullptr,
-                  loss_ring.has_value() ? loss_ring->data_ptr<float>() : nullptr,
-                  loss_ring.has_value() ? (int)loss_ring->numel() : 1, clip > 0 ? f32p(*norm_part) : nullptr,
-                  stream()) == 0);
+  TORCH_CHECK(pio::adamw_grouped_launch(b.p, b.g, b.m, b.v, b.shadow, b.n, b.hyper, chunks, chunk_tab.size(0), tg, (int)T,
+                                        (int)groups, (float)clip, (float)gscale, l2 ? 1 : 0, zero_grad ? 1 : 0, lr.src,
+                                        lr.ring, lr.n, norm_part_arg("adamw_grouped", clip, norm_part), stream()) == 0);
 }
 
 // weight EMA over a flat fp32 buffer (csrc/ema.hip): ema ← ema + hyper[5]·(w − ema); hyper[5] = 0
@@ -1975,8 +1979,7 @@ void ema_update(Tensor ema, Tensor w, Tensor hyper) {
               "ema_update: ema and w contiguous fp32 of one size, on the device of hyper");
   TORCH_CHECK(hyper.numel() >= 8, "ema_update: hyper of 8 floats (hyper[5] = 1 - decay)");
   TORCH_CHECK(ema.numel() % 4 == 0, "ema_update: the element count must be a multiple of 4, got ", ema.numel());
-  TORCH_CHECK(((reinterpret_cast<uintptr_t>(ema.data_ptr()) | reinterpret_cast<uintptr_t>(w.data_ptr())) & 15) == 0,
-              "ema_update: the buffers must be 16-byte aligned");
+  TORCH_CHECK(aligned(ema.data_ptr(), 16) && aligned(w.data_ptr(), 16), "ema_update: the buffers must be 16-byte aligned");
   TORCH_CHECK(ema.numel() == 0 || ema.data_ptr() != w.data_ptr(), "ema_update: ema and w must be different buffers");
   pio::ema_update_launch(ema.data_ptr<float>(), f32p(w), ema.numel(), f32p(hyper), stream());
 }
@@ -1996,8 +1999,7 @@ void ema_swap(Tensor w, Tensor ema, OptT shadow) {
                 "ema_swap: shadow contiguous bf16 of w's size on its device");
     sp = reinterpret_cast<uint16_t*>(shadow->data_ptr());
   }
-  TORCH_CHECK(((reinterpret_cast<uintptr_t>(w.data_ptr()) | reinterpret_cast<uintptr_t>(ema.data_ptr())) & 15) == 0 &&
-                  (reinterpret_cast<uintptr_t>(sp) & 7) == 0,
+  TORCH_CHECK(aligned(w.data_ptr(), 16) && aligned(ema.data_ptr(), 16) && aligned(sp, 8),
               "ema_swap: the buffers must be 16-byte aligned (the shadow 8-byte)");
   TORCH_CHECK(w.numel() == 0 || w.data_ptr() != ema.data_ptr(), "ema_swap: w and ema must be different buffers");
   pio::ema_swap_launch(w.data_ptr<float>(), ema.data_ptr<float>(), sp, w.numel(), stream());

@@ -1,15 +1,12 @@
 // Memory-bound kernels: text embedding (+ scale + learned position table) forward/backward,
-// BERT masking, fused multi-tensor AdamW over the flat parameter buffer.
+// BERT masking, casts, row gather / index-add, batch sums.
 //
 // Reference parity:
 //   TextInputAdapter  emb(x)·sqrt(C) + pos[:L]          perceiver/adapter.py:127-133  (SURVEY K-01)
 //   TextMasking       80/10/10 BERT masking, labels      perceiver/model.py:265-293    (SURVEY K-02)
-//   AdamW (torch.optim defaults, decoupled wd)           scripts/cli.py:43, lightning.py:44-55 (SURVEY K-15)
 // MI355X notes: one launch each, vectorised 16-B accesses on the streaming paths; the
-// masking kernel needs no host sync (the reference's nonzero/sum syncs disappear); AdamW
-// reads hyper-parameters (lr, step, grad-norm clip factor) from device memory so the
-// whole optimizer step can be captured in a hipGraph, and writes the bf16 weight shadow
-// that the GEMM kernels consume in the same pass.
+// masking kernel needs no host sync (the reference's nonzero/sum syncs disappear).  The
+// optimizer step over the flat parameter buffer lives in optim.hip.
 #include "common.h"
 
 namespace pio {
@@ -224,240 +221,6 @@ __global__ void text_mask_kernel(const int64_t* __restrict__ x, const bool* __re
   }
 }
 
-// sum of squares of the flat gradient (clip_grad_norm): Σ g² in fixed order, no atomics: block b writes its partial to part[b] (kSumsqBlocks blocks,
-// grid-stride, 8 independent 16-byte loads in flight per thread); the AdamW kernels sum the
-// partials themselves (adam_clip_scale).  The previous single-address atomic per block put
-// 2048 serialised adds at the end of an HBM-bound pass (36 µs for the 68 MB LArTPC gradient).
-__global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g, long long n, float* __restrict__ part) {
-  float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  const long long n4 = ((reinterpret_cast<uintptr_t>(g) & 15) == 0) ? n >> 2 : 0;
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  const float4* g4 = reinterpret_cast<const float4*>(g);
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  for (; i + 7 * stride < n4; i += 8 * stride) {
-    float4 a[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) a[k] = g4[i + k * stride];
-#pragma unroll
-    for (int k = 0; k < 8; ++k)
-      s[k] = fmaf(a[k].x, a[k].x, fmaf(a[k].y, a[k].y, fmaf(a[k].z, a[k].z, fmaf(a[k].w, a[k].w, s[k]))));
-  }
-  for (; i < n4; i += stride) {
-    const float4 a = g4[i];
-    s[0] = fmaf(a.x, a.x, fmaf(a.y, a.y, fmaf(a.z, a.z, fmaf(a.w, a.w, s[0]))));
-  }
-  for (long long j = (n4 << 2) + (long long)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += stride) {
-    const float v = g[j];
-    s[1] = fmaf(v, v, s[1]);
-  }
-  float t = ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]));
-  t = wave_sum(t);
-  __shared__ float red[4];
-  if (lane_id() == 0) red[wave_id()] = t;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// the clip factor of a step from sumsq_kernel's partials, in a fixed order (every block of the
-// AdamW grid the same value): wave 0 sums the kSumsqBlocks partials, LDS broadcast
-__device__ __forceinline__ float adam_clip_scale(const float* __restrict__ part, float clip, float gscale) {
-  __shared__ float s_norm2;
-  if (threadIdx.x < 64) {
-    float t = 0.f;
-#pragma unroll
-    for (int k = 0; k < kSumsqBlocks / 64; ++k) t += part[threadIdx.x + 64 * k];
-    t = wave_sum(t);
-    if (threadIdx.x == 0) s_norm2 = t;
-  }
-  __syncthreads();
-  const float norm = sqrtf(s_norm2) * gscale;
-  const float f = clip / (norm + 1e-6f);
-  return f < 1.f ? f : 1.f;
-}
-
-// hyper[0] = lr, [1] = step (already incremented), [3] = beta1, [4] = beta2, [7] = loss-ring slot — read from device memory so schedulers can
-// change them between replays of a captured step.
-// loss_src (optional): the step's scalar loss, copied by thread 0 into loss_ring[hyper[7] % ring_n]
-// (the step engine hands that slot back as the step's loss: no separate copy launch per step)
-// zero_g: the gradient is cleared as it is consumed (a replayed step then needs no separate
-// zero fill of the flat gradient buffer before its backward)
-// clip > 0: the gradient's sum of squares comes as sumsq_kernel's per-block partials (norm_part)
-__global__ void adamw_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
-                             float* __restrict__ v, uint16_t* __restrict__ shadow, long long n,
-                             const float* __restrict__ hyper, float eps, float wd, float clip, float gscale,
-                             int l2, int zero_g, const float* __restrict__ loss_src, float* __restrict__ loss_ring,
-                             int ring_n, const float* __restrict__ norm_part) {
-  const float lr = hyper[0], step = hyper[1], beta1 = hyper[3], beta2 = hyper[4];
-  if (loss_src != nullptr && blockIdx.x == 0 && threadIdx.x == 0) loss_ring[(int)hyper[7] % ring_n] = *loss_src;
-  const float bc1 = 1.f - powf(beta1, step), bc2 = 1.f - powf(beta2, step);
-  // g holds the all-reduced SUM over ranks (gscale = 1 / world makes it the mean): the clip
-  // threshold applies to the norm of the MEAN gradient, as in single-process training
-  float gs = gscale;
-  if (clip > 0.f) gs *= adam_clip_scale(norm_part, clip, gscale);
-  const float step_size = lr / bc1;
-  const float bc2s = sqrtf(bc2);
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    float pi = p[i];
-    // l2 (torch.optim.Adam weight_decay): the decay joins the (clipped) gradient; else AdamW's
-    // decoupled decay of the weights
-    const float g0 = g[i];
-    if (zero_g) g[i] = 0.f;
-    const float gi = l2 ? fmaf(wd, pi, g0 * gs) : g0 * gs;
-    if (!l2) pi *= 1.f - lr * wd;
-    const float mi = beta1 * m[i] + (1.f - beta1) * gi;
-    const float vi = beta2 * v[i] + (1.f - beta2) * gi * gi;
-    m[i] = mi;
-    v[i] = vi;
-    pi -= step_size * mi / (sqrtf(vi) / bc2s + eps);
-    p[i] = pi;
-    if (shadow) shadow[i] = f2bf(pi);
-  }
-}
-
-// the same update on 4 elements per thread (16-byte loads / stores; every pointer 16-byte
-// aligned, the shadow 8-byte aligned, n % 4 == 0 — checked by the launcher): a quarter of the
-// memory instructions of the scalar loop, which is issue-bound at ≈40 % of HBM bandwidth
-__global__ __launch_bounds__(256) void adamw4_kernel(float4* __restrict__ p, float4* __restrict__ g,
-                                                     float4* __restrict__ m, float4* __restrict__ v,
-                                                     uint2* __restrict__ shadow, long long n4,
-                                                     const float* __restrict__ hyper, float eps, float wd, float clip,
-                                                     float gscale, int l2, int zero_g, const float* __restrict__ loss_src,
-                                                     float* __restrict__ loss_ring, int ring_n,
-                                                     const float* __restrict__ norm_part) {
-  const float lr = hyper[0], step = hyper[1], beta1 = hyper[3], beta2 = hyper[4];
-  if (loss_src != nullptr && blockIdx.x == 0 && threadIdx.x == 0) loss_ring[(int)hyper[7] % ring_n] = *loss_src;
-  const float bc1 = 1.f - powf(beta1, step), bc2 = 1.f - powf(beta2, step);
-  float gs = gscale;
-  if (clip > 0.f) gs *= adam_clip_scale(norm_part, clip, gscale);
-  const float step_size = lr / bc1;
-  const float bc2s = sqrtf(bc2);
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
-    const float4 p4 = p[i], g4 = g[i], m4 = m[i], v4 = v[i];
-    if (zero_g) g[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    const float pa[4] = {p4.x, p4.y, p4.z, p4.w}, ga[4] = {g4.x, g4.y, g4.z, g4.w};
-    const float ma[4] = {m4.x, m4.y, m4.z, m4.w}, va[4] = {v4.x, v4.y, v4.z, v4.w};
-    float po[4], mo[4], vo[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {  // the scalar kernel's arithmetic, element by element
-      float pi = pa[e];
-      const float gi = l2 ? fmaf(wd, pi, ga[e] * gs) : ga[e] * gs;
-      if (!l2) pi *= 1.f - lr * wd;
-      mo[e] = beta1 * ma[e] + (1.f - beta1) * gi;
-      vo[e] = beta2 * va[e] + (1.f - beta2) * gi * gi;
-      po[e] = pi - step_size * mo[e] / (sqrtf(vo[e]) / bc2s + eps);
-    }
-    m[i] = make_float4(mo[0], mo[1], mo[2], mo[3]);
-    v[i] = make_float4(vo[0], vo[1], vo[2], vo[3]);
-    p[i] = make_float4(po[0], po[1], po[2], po[3]);
-    if (shadow) shadow[i] = make_uint2(pack2(po[0], po[1]), pack2(po[2], po[3]));
-  }
-}
-
-// AdamW with per-group lr / weight decay / eps (ops/optim.py FusedAdamW with several parameter
-// groups).  The flat buffers carry no tensor boundaries, so the host hands over the chunk table of
-// the LAMB update (chunks (C, 3) int64 = start, length, tensor: at most kAdamChunk elements, never
-// across a tensor boundary, the padding between tensors in no chunk) and tgroup (T,) int32 =
-// tensor → group.  Group j's words sit behind the 8 global ones: hyper[8 + 4j .. ] = lr, weight
-// decay, eps, reserved.  step / betas / clip factor / gscale / l2 / zero_g / loss ring are global,
-// and every element takes adamw4_kernel's arithmetic (adamw_elem), so with equal options in
-// every group the result is bitwise adamw4_kernel's.  A workgroup walks chunks grid-stride: 256
-// threads × float4, every load of a chunk in flight before the arithmetic, a scalar tail for
-// length % 4.  Padding is neither read nor written; no atomics.  A chunk that does not fit the
-// buffers or a group id outside [0, G) is skipped (checked builds flag kErrOptTable).
-constexpr int kAdamChunk = 4096;                  // elements; ops/optim.py LAMB_CHUNK
-constexpr int kAdamIter = kAdamChunk / (4 * 256);  // float4 per thread of a full chunk
-constexpr int kAdamGroupBase = 8, kAdamGroupWords = 4, kAdamMaxGroups = 8;
-
-// adamw4_kernel's update of one element with the multiply-adds the compiler fuses there under
-// -ffp-contract=fast spelled out (decay = fma(−wd, lr, 1), m ← fma(β1, m, (1−β1)·ĝ), v ← fma(β2, v,
-// ((1−β2)·ĝ)·ĝ), everything else rounded on its own) and contraction off, so that the vector path
-// and the tail of the grouped kernel cannot come out differently from it or from each other
-// (tests/test_param_groups_gpu.py compares the two kernels bit for bit)
-__device__ __forceinline__ void adamw_elem(float pi, float g0, float mi, float vi, float gs, float wd, float decay,
-                                           float beta1, float omb1, float beta2, float omb2, float step_size, float bc2s,
-                                           float eps, int l2, float& po, float& mo, float& vo) {
-#pragma clang fp contract(off)
-  const float gi = l2 ? fmaf(wd, pi, g0 * gs) : g0 * gs;
-  if (!l2) pi *= decay;
-  mo = fmaf(beta1, mi, omb1 * gi);
-  vo = fmaf(beta2, vi, (omb2 * gi) * gi);
-  po = pi - step_size * mo / (sqrtf(vo) / bc2s + eps);
-}
-
-__global__ __launch_bounds__(256) void adamw_grouped_kernel(
-    float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-    uint16_t* __restrict__ shadow, long long n, const float* __restrict__ hyper, const long long* __restrict__ chunks,
-    long long C, const int* __restrict__ tgroup, int T, int G, float clip, float gscale, int l2, int zero_g,
-    const float* __restrict__ loss_src, float* __restrict__ loss_ring, int ring_n, const float* __restrict__ norm_part) {
-  const float step = hyper[1], beta1 = hyper[3], beta2 = hyper[4];
-  if (loss_src != nullptr && blockIdx.x == 0 && threadIdx.x == 0) loss_ring[(int)hyper[7] % ring_n] = *loss_src;
-  const float bc1 = 1.f - powf(beta1, step), bc2 = 1.f - powf(beta2, step);
-  float gs = gscale;
-  if (clip > 0.f) gs *= adam_clip_scale(norm_part, clip, gscale);
-  const float bc2s = sqrtf(bc2), omb1 = 1.f - beta1, omb2 = 1.f - beta2;
-  for (long long c = blockIdx.x; c < C; c += gridDim.x) {  // uniform over the block
-    const long long start = chunks[3 * c], len = chunks[3 * c + 1], tid = chunks[3 * c + 2];
-    bool ok = start >= 0 && (start & 3) == 0 && len >= 0 && len <= kAdamChunk && start + len <= n && tid >= 0 && tid < T;
-    const int grp = ok ? tgroup[tid] : 0;
-    ok = ok && grp >= 0 && grp < G;
-    if (!ok) {
-      if (threadIdx.x == 0) pio_flag(kErrOptTable);
-      continue;
-    }
-    const float* hg = hyper + kAdamGroupBase + kAdamGroupWords * grp;
-    const float lr = hg[0], wd = hg[1], eps = hg[2];
-    const float step_size = lr / bc1, decay = fmaf(-wd, lr, 1.f);
-    const int len4 = (int)len >> 2;
-    float4* p4 = reinterpret_cast<float4*>(p + start);
-    float4* g4 = reinterpret_cast<float4*>(g + start);
-    float4* m4 = reinterpret_cast<float4*>(m + start);
-    float4* v4 = reinterpret_cast<float4*>(v + start);
-    uint2* s2 = shadow ? reinterpret_cast<uint2*>(shadow + start) : nullptr;
-    float4 P[kAdamIter], Gr[kAdamIter], M[kAdamIter], V[kAdamIter];
-#pragma unroll
-    for (int k = 0; k < kAdamIter; ++k) {
-      const int i = threadIdx.x + 256 * k;
-      if (i < len4) {
-        P[k] = p4[i];
-        Gr[k] = g4[i];
-        M[k] = m4[i];
-        V[k] = v4[i];
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < kAdamIter; ++k) {
-      const int i = threadIdx.x + 256 * k;
-      if (i < len4) {
-        if (zero_g) g4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        const float pa[4] = {P[k].x, P[k].y, P[k].z, P[k].w}, ga[4] = {Gr[k].x, Gr[k].y, Gr[k].z, Gr[k].w};
-        const float ma[4] = {M[k].x, M[k].y, M[k].z, M[k].w}, va[4] = {V[k].x, V[k].y, V[k].z, V[k].w};
-        float po[4], mo[4], vo[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          adamw_elem(pa[e], ga[e], ma[e], va[e], gs, wd, decay, beta1, omb1, beta2, omb2, step_size, bc2s, eps, l2, po[e],
-                     mo[e], vo[e]);
-        m4[i] = make_float4(mo[0], mo[1], mo[2], mo[3]);
-        v4[i] = make_float4(vo[0], vo[1], vo[2], vo[3]);
-        p4[i] = make_float4(po[0], po[1], po[2], po[3]);
-        if (s2) s2[i] = make_uint2(pack2(po[0], po[1]), pack2(po[2], po[3]));
-      }
-    }
-    // a tensor's last chunk: up to 3 elements past the last whole float4
-    const int t = (len4 << 2) + threadIdx.x;
-    if (t < (int)len) {
-      const long long j = start + t;
-      const float g0 = g[j];
-      if (zero_g) g[j] = 0.f;
-      float pi, mi, vi;
-      adamw_elem(p[j], g0, m[j], v[j], gs, wd, decay, beta1, omb1, beta2, omb2, step_size, bc2s, eps, l2, pi, mi, vi);
-      m[j] = mi;
-      v[j] = vi;
-      p[j] = pi;
-      if (shadow) shadow[j] = f2bf(pi);
-    }
-  }
-}
-
 __global__ void cast_bf16_kernel(const float* __restrict__ x, uint16_t* __restrict__ y, long long n) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
     y[i] = f2bf(x[i]);
@@ -509,10 +272,6 @@ void text_mask_launch(const int64_t* x, const bool* pad, int64_t* state, int64_t
   hipLaunchKernelGGL(text_mask_kernel, grid_for(n), dim3(256), 0, st, x, pad, state, xm, labels, n, unk_id, mask_id, p, lo,
                      range, advance);
 }
-void sumsq_launch(const float* g, long long n, float* part, hipStream_t st) {
-  hipLaunchKernelGGL(sumsq_kernel, dim3(kSumsqBlocks), dim3(256), 0, st, g, n, part);
-}
-
 // dst[idx[r]][:] += src[r][:] — the backward of a row gather (rows of idx may repeat: fp32
 // atomics; an index outside dst is skipped).  One thread per 4 columns.
 __global__ void index_add_rows_kernel(float* __restrict__ dst, long long nrows, const int64_t* __restrict__ idx,
@@ -608,57 +367,6 @@ void batch_sum2_launch(const float* a, const float* b, float* oa, float* ob, int
   const long long na4 = a ? na / 4 : 0, nb4 = nb / 4;
   hipLaunchKernelGGL(batch_sum2_kernel, dim3((unsigned)((na4 + nb4 + 63) / 64)), dim3(256), 0, st, a, b, oa, ob, B, na4,
                      nb4, acc_b);
-}
-void adamw_launch(float* p, float* g, float* m, float* v, uint16_t* shadow, long long n, const float* hyper,
-                  float eps, float wd, float clip, float gscale, int l2, int zero_g, const float* loss_src,
-                  float* loss_ring, int ring_n, const float* norm_part, hipStream_t st) {
-  const bool vec = n % 4 == 0 && ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) |
-                                    reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v)) & 15) == 0 &&
-                   (reinterpret_cast<uintptr_t>(shadow) & 7) == 0;
-  if (vec)
-    hipLaunchKernelGGL(adamw4_kernel, grid_for(n / 4), dim3(256), 0, st, reinterpret_cast<float4*>(p),
-                       reinterpret_cast<float4*>(g), reinterpret_cast<float4*>(m), reinterpret_cast<float4*>(v),
-                       reinterpret_cast<uint2*>(shadow), n / 4, hyper, eps, wd, clip, gscale, l2, zero_g, loss_src,
-                       loss_ring, ring_n, norm_part);
-  else
-    hipLaunchKernelGGL(adamw_kernel, grid_for(n), dim3(256), 0, st, p, g, m, v, shadow, n, hyper, eps, wd, clip, gscale,
-                       l2, zero_g, loss_src, loss_ring, ring_n, norm_part);
-}
-// p, g, m, v 16-byte aligned, shadow 8-byte aligned, hyper of 8 + 4 G floats (checked by the
-// binding); C chunks, T tensors, 1 ≤ G ≤ 8.  At most 2048 workgroups (8 per CU) walk the chunks.
-int adamw_grouped_launch(float* p, float* g, float* m, float* v, uint16_t* shadow, long long n, const float* hyper,
-                         const long long* chunks, long long C, const int* tgroup, int T, int G, float clip, float gscale,
-                         int l2, int zero_g, const float* loss_src, float* loss_ring, int ring_n,
-                         const float* norm_part, hipStream_t st) {
-  if (G < 1 || G > kAdamMaxGroups) return -1;
-  if (C <= 0 || T <= 0) return 0;
-  const unsigned blocks = (unsigned)(C < 2048 ? C : 2048);
-  hipLaunchKernelGGL(adamw_grouped_kernel, dim3(blocks), dim3(256), 0, st, p, g, m, v, shadow, n, hyper, chunks, C, tgroup,
-                     T, G, clip, gscale, l2, zero_g, loss_src, loss_ring, ring_n, norm_part);
-  return 0;
-}
-// grad[i] += Σ_r rep[r][i], rep[r][i] ← 0 (replicated gradient accumulators, see ops/optim.py)
-__global__ void fold_replicas_kernel(float* __restrict__ grad, float* __restrict__ rep, long long n, int nrep) {
-  const long long n4 = n >> 2;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
-    float4 acc = reinterpret_cast<float4*>(grad)[i];
-    for (int r = 0; r < nrep; ++r) {
-      float4* p = reinterpret_cast<float4*>(rep + r * n) + i;
-      const float4 v = *p;
-      acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-      *p = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    reinterpret_cast<float4*>(grad)[i] = acc;
-  }
-  for (long long i = (n4 << 2) + (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (long long)gridDim.x * blockDim.x) {
-    float acc = grad[i];
-    for (int r = 0; r < nrep; ++r) { acc += rep[r * n + i]; rep[r * n + i] = 0.f; }
-    grad[i] = acc;
-  }
-}
-void fold_replicas_launch(float* grad, float* rep, long long n, int nrep, hipStream_t st) {
-  hipLaunchKernelGGL(fold_replicas_kernel, grid_for((n + 3) / 4), dim3(256), 0, st, grad, rep, n, nrep);
 }
 
 // standalone form of a SlabJob (common.h): the reductions still pending at the end of a

@@ -60,7 +60,7 @@ struct SlabJob {
   float* zero_p;
   long long zero_n4;
 };
-// blocks of the gradient sum-of-squares pass: one fp32 partial each (elementwise.hip sumsq_kernel)
+// blocks of the gradient sum-of-squares pass: one fp32 partial each (optim.hip sumsq_kernel)
 constexpr int kSumsqBlocks = 512;
 
 // fp32 gradient targets of the post-attention block (views of the flat gradient buffer).
@@ -331,23 +331,12 @@ void embed_bwd_sorted_launch(const int64_t* sorted_ids, const int64_t* perm, con
                              int C, float scale, hipStream_t st);
 void text_mask_launch(const int64_t* x, const bool* pad, int64_t* state, int64_t* xm, int64_t* labels, long long n,
                       int unk_id, int mask_id, float p, int lo, uint32_t range, int advance, hipStream_t st);
-void sumsq_launch(const float* g, long long n, float* part, hipStream_t st);
 void index_add_rows_launch(float* dst, long long nrows, const int64_t* idx, const float* src, long long R, int C,
                            hipStream_t st);
 void gather_rows_launch(float* out, const float* src, long long nrows, const int64_t* idx, long long R, int C,
                         hipStream_t st);
 void batch_sum2_launch(const float* a, const float* b, float* oa, float* ob, int B, long long na, long long nb, int acc_b,
                        hipStream_t st);
-void adamw_launch(float* p, float* g, float* m, float* v, uint16_t* shadow, long long n, const float* hyper,
-                  float eps, float wd, float clip, float gscale, int l2, int zero_g, const float* loss_src,
-                  float* loss_ring, int ring_n, const float* norm_part, hipStream_t st);
-// AdamW with per-group lr / weight decay / eps over the LAMB chunk table (chunks (C, 3) int64,
-// tgroup (T,) int32 = tensor → group, hyper of 8 + 4 G floats); -1 for G outside [1, 8]
-int adamw_grouped_launch(float* p, float* g, float* m, float* v, uint16_t* shadow, long long n, const float* hyper,
-                         const long long* chunks, long long C, const int* tgroup, int T, int G, float clip, float gscale,
-                         int l2, int zero_g, const float* loss_src, float* loss_ring, int ring_n,
-                         const float* norm_part, hipStream_t st);
-void fold_replicas_launch(float* grad, float* rep, long long n, int nrep, hipStream_t st);
 void slab_reduce_launch(const SlabJob& job, hipStream_t st);
 void reduce_probe_launch(const float* x, float* out, hipStream_t st);
 void cast_bf16_launch(const float* x, uint16_t* y, long long n, hipStream_t st);
@@ -364,6 +353,7 @@ void ema_update_launch(float* ema, const float* w, long long n, const float* hyp
 // w ↔ ema in place, shadow (may be null) ← bf16(new w); 16-byte aligned (shadow 8), n % 4 == 0
 void ema_swap_launch(float* w, float* ema, uint16_t* shadow, long long n, hipStream_t st);
 // ---- lamb.hip ----
+// elements per chunk of the chunk table (lamb_launch, adamw_grouped_launch): the extension's LAMB_CHUNK
 int lamb_chunk_elems();
 // p, g, m, v 16-byte aligned, shadow 8-byte aligned (checked by the binding); C chunks, T tensors;
 // tgroup (T,) tensor → group with hyper of 8 + 4 G floats, or null: every tensor in group 0
@@ -388,6 +378,19 @@ void ce_bwd_launch(int C, const uint16_t* Hm, const int64_t* labels, const uint1
                    const float* lse, const float* gout, const float* count, int M, int V, float* dH, long long dh_rows,
                    const int64_t* rowmap, float* dW, float* db, int accumulate, float* slab, int det, hipStream_t st);
 unsigned check_errors_mlm_head(bool reset);
+// ---- optim.hip ----
+void sumsq_launch(const float* g, long long n, float* part, hipStream_t st);
+void adamw_launch(float* p, float* g, float* m, float* v, uint16_t* shadow, long long n, const float* hyper,
+                  float eps, float wd, float clip, float gscale, int l2, int zero_g, const float* loss_src,
+                  float* loss_ring, int ring_n, const float* norm_part, hipStream_t st);
+// AdamW with per-group lr / weight decay / eps over the LAMB chunk table (chunks (C, 3) int64,
+// tgroup (T,) int32 = tensor → group, hyper of 8 + 4 G floats); -1 for G outside [1, 8]
+int adamw_grouped_launch(float* p, float* g, float* m, float* v, uint16_t* shadow, long long n, const float* hyper,
+                         const long long* chunks, long long C, const int* tgroup, int T, int G, float clip, float gscale,
+                         int l2, int zero_g, const float* loss_src, float* loss_ring, int ring_n,
+                         const float* norm_part, hipStream_t st);
+void fold_replicas_launch(float* grad, float* rep, long long n, int nrep, hipStream_t st);
+unsigned check_errors_optim(bool reset);
 // ---- pe_proj.hip ----
 int pe_grad_splits(int M);
 void pe_grads_launch(const uint16_t* E, const float* D, int M, int Kp, int O, const float* part, int nblk, float* slab,

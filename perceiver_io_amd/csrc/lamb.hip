@@ -1,9 +1,7 @@
 // Fused LAMB over the flat parameter space (ops/optim.py FusedLamb): layer-wise trust ratios
 // ‖w‖/‖u‖ and per-tensor weight decay on top of the flat fp32 buffers.
 //
-// The flat buffers carry no tensor boundaries, so the host cuts every tensor range into chunks of
-// at most kLambChunk elements (never across a tensor boundary; padding between tensors belongs to
-// no chunk) and hands the kernels two device tables:
+// The kernels walk the chunk table of the flat buffers (optim_common.h) and two per-tensor tables:
 //   chunks (C, 3) int64: start element, length, tensor id
 //   tensors (T, 2) int32: first chunk, chunk count;  topt (T, 2) fp32: weight decay, adapt (0 / 1)
 // One step is three launches:
@@ -16,64 +14,20 @@
 //                        per element instead of 4 B written + 8 B read for a stored u) and writes
 //                        w ← w − lr·trust·u with its bf16 shadow
 // No atomics and fixed summation orders everywhere: results are bitwise repeatable.  Both chunk
-// kernels form u with lamb_u() from the same operands; this translation unit is compiled with
-// -ffp-contract=off (csrc/build.py PER_FILE_FLAGS), so the compiler cannot contract its
-// multiply-adds differently in the two kernels — the only fused operations are the explicit fmaf
-// calls — and the u whose norm set the trust ratio is bit for bit the u that is applied.
-// lr / step / betas come from `hyper` in device memory (the layout of adamw_kernel), so a
+// kernels form u with lamb_u() (optim_common.h) from the same operands; this translation unit is
+// compiled with -ffp-contract=off (csrc/build.py PER_FILE_FLAGS), so the compiler cannot contract
+// its multiply-adds differently in the two kernels — the only fused operations are the explicit
+// fmaf calls — and the u whose norm set the trust ratio is bit for bit the u that is applied.
+// lr / step / betas come from `hyper` in device memory (optim_common.h opt_step), so a
 // replayed graph follows the scheduler.
-#include "common.h"
+#include "optim_common.h"
 
 namespace pio {
-
-constexpr int kLambChunk = 4096;                 // elements; ops/optim.py LAMB_CHUNK
-constexpr int kLambIter = kLambChunk / (4 * 256);  // float4 per thread of a full chunk
-
-// the clip factor from sumsq_kernel's partials: elementwise.hip adam_clip_scale, same order
-__device__ __forceinline__ float lamb_clip_scale(const float* __restrict__ part, float clip, float gscale) {
-  __shared__ float s_norm2;
-  if (threadIdx.x < 64) {
-    float t = 0.f;
-#pragma unroll
-    for (int k = 0; k < kSumsqBlocks / 64; ++k) t += part[threadIdx.x + 64 * k];
-    t = wave_sum(t);
-    if (threadIdx.x == 0) s_norm2 = t;
-  }
-  __syncthreads();
-  const float norm = sqrtf(s_norm2) * gscale;
-  const float f = clip / (norm + 1e-6f);
-  return f < 1.f ? f : 1.f;
-}
 
 // 1 − β^t without the cancellation of 1.f − powf(β, t) (β2 = 0.999, t = 3: one ulp of β^t is 1e-5
 // of the result, and the trust ratio inherits it)
 __device__ __forceinline__ float lamb_bias_correction(float beta, float step) {
   return -expm1f(step * logf(beta));
-}
-
-// u of one element from the NEW moments and the OLD weight (both passes call exactly this)
-__device__ __forceinline__ float lamb_u(float w, float m, float v, float bc1, float bc2s, float eps, float wd) {
-  const float r = (m / bc1) / (sqrtf(v) / bc2s + eps);
-  return fmaf(wd, w, r);
-}
-
-struct LambChunk {
-  long long start;
-  int len, tid;
-  bool ok;
-};
-// a chunk of the table, validated against the buffers (a block whose entry does not fit does
-// nothing: the tables are built by the host once, but nothing here may write out of bounds)
-__device__ __forceinline__ LambChunk lamb_chunk(const long long* __restrict__ chunks, long long n, int T) {
-  const long long* c = chunks + 3 * (long long)blockIdx.x;
-  LambChunk k;
-  k.start = c[0];
-  const long long len = c[1], tid = c[2];
-  k.ok = k.start >= 0 && (k.start & 3) == 0 && len >= 0 && len <= kLambChunk && k.start + len <= n && tid >= 0 &&
-         tid < T;
-  k.len = k.ok ? (int)len : 0;
-  k.tid = k.ok ? (int)tid : 0;
-  return k;
 }
 
 // fixed-order block sum of two values (256 threads): lane butterflies, then the 4 wave results
@@ -90,18 +44,15 @@ __device__ __forceinline__ void block_sum2(float& a, float& b) {
   b = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
 }
 
-// pass 1.  hyper / loss_src / loss_ring / zero_g / clip as in adamw_kernel (elementwise.hip)
+// pass 1.  hyper / loss_src / loss_ring / zero_g / clip as in adamw_kernel (optim.hip)
 __global__ __launch_bounds__(256) void lamb_moments_kernel(
     const float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long long n,
     const float* __restrict__ hyper, const long long* __restrict__ chunks, const float* __restrict__ topt, int T,
     float* __restrict__ partials, float eps, float clip, float gscale, int zero_g, const float* __restrict__ loss_src,
     float* __restrict__ loss_ring, int ring_n, const float* __restrict__ norm_part) {
-  const float step = hyper[1], beta1 = hyper[3], beta2 = hyper[4];
-  if (loss_src != nullptr && blockIdx.x == 0 && threadIdx.x == 0) loss_ring[(int)hyper[7] % ring_n] = *loss_src;
-  const float bc1 = lamb_bias_correction(beta1, step), bc2s = sqrtf(lamb_bias_correction(beta2, step));
-  float gs = gscale;
-  if (clip > 0.f) gs *= lamb_clip_scale(norm_part, clip, gscale);
-  const LambChunk c = lamb_chunk(chunks, n, T);
+  const OptStep s = opt_step(hyper, clip, gscale, loss_src, loss_ring, ring_n, norm_part);
+  const float bc1 = lamb_bias_correction(s.beta1, s.step), bc2s = sqrtf(lamb_bias_correction(s.beta2, s.step));
+  const OptChunk c = opt_chunk(chunks, blockIdx.x, n, T);
   float sw = 0.f, su = 0.f;
   if (c.ok) {
     const float wd = topt[2 * c.tid];
@@ -110,9 +61,9 @@ __global__ __launch_bounds__(256) void lamb_moments_kernel(
     float4* g4 = reinterpret_cast<float4*>(g + c.start);
     float4* m4 = reinterpret_cast<float4*>(m + c.start);
     float4* v4 = reinterpret_cast<float4*>(v + c.start);
-    float4 P[kLambIter], G[kLambIter], M[kLambIter], V[kLambIter];
+    float4 P[kOptIter], G[kOptIter], M[kOptIter], V[kOptIter];
 #pragma unroll
-    for (int k = 0; k < kLambIter; ++k) {  // every load of the chunk in flight before the arithmetic
+    for (int k = 0; k < kOptIter; ++k) {  // every load of the chunk in flight before the arithmetic
       const int i = threadIdx.x + 256 * k;
       if (i < len4) {
         P[k] = p4[i];
@@ -122,7 +73,7 @@ __global__ __launch_bounds__(256) void lamb_moments_kernel(
       }
     }
 #pragma unroll
-    for (int k = 0; k < kLambIter; ++k) {
+    for (int k = 0; k < kOptIter; ++k) {
       const int i = threadIdx.x + 256 * k;
       if (i < len4) {
         if (zero_g) g4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -131,9 +82,7 @@ __global__ __launch_bounds__(256) void lamb_moments_kernel(
         float mo[4], vo[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const float gi = ga[e] * gs;
-          mo[e] = beta1 * ma[e] + (1.f - beta1) * gi;
-          vo[e] = beta2 * va[e] + (1.f - beta2) * gi * gi;
+          lamb_moments(ga[e], ma[e], va[e], s.gs, s.beta1, s.beta2, mo[e], vo[e]);
           const float u = lamb_u(pa[e], mo[e], vo[e], bc1, bc2s, eps, wd);
           sw = fmaf(pa[e], pa[e], sw);
           su = fmaf(u, u, su);
@@ -146,10 +95,10 @@ __global__ __launch_bounds__(256) void lamb_moments_kernel(
     const int t = (len4 << 2) + threadIdx.x;
     if (t < c.len) {
       const long long j = c.start + t;
-      const float w = p[j], gi = g[j] * gs;
+      const float w = p[j], g0 = g[j];
       if (zero_g) g[j] = 0.f;
-      const float mi = beta1 * m[j] + (1.f - beta1) * gi;
-      const float vi = beta2 * v[j] + (1.f - beta2) * gi * gi;
+      float mi, vi;
+      lamb_moments(g0, m[j], v[j], s.gs, s.beta1, s.beta2, mi, vi);
       m[j] = mi;
       v[j] = vi;
       const float u = lamb_u(w, mi, vi, bc1, bc2s, eps, wd);
@@ -210,10 +159,10 @@ __global__ __launch_bounds__(256) void lamb_apply_kernel(float* __restrict__ p, 
                                                          const int* __restrict__ tgroup, int G) {
   const float step = hyper[1], beta1 = hyper[3], beta2 = hyper[4];
   const float bc1 = lamb_bias_correction(beta1, step), bc2s = sqrtf(lamb_bias_correction(beta2, step));
-  const LambChunk c = lamb_chunk(chunks, n, T);
+  const OptChunk c = opt_chunk(chunks, blockIdx.x, n, T);
   if (!c.ok) return;
   // the tensor's lr: its group's word behind the 8 global ones (hyper[8 + 4 j], the layout of
-  // adamw_grouped_kernel); without a group table every tensor takes group 0's, hyper[0]
+  // optim.hip adamw_grouped_kernel); without a group table every tensor takes group 0's, hyper[0]
   float lr = hyper[0];
   if (tgroup != nullptr) {
     const int grp = tgroup[c.tid];
@@ -221,7 +170,7 @@ __global__ __launch_bounds__(256) void lamb_apply_kernel(float* __restrict__ p, 
       if (threadIdx.x == 0) pio_flag(kErrOptTable);
       return;
     }
-    lr = hyper[8 + 4 * grp];
+    lr = hyper[kOptGroupBase + kOptGroupWords * grp];
   }
   const float wd = topt[2 * c.tid];
   const float a = -(lr * trust[c.tid]);
@@ -230,9 +179,9 @@ __global__ __launch_bounds__(256) void lamb_apply_kernel(float* __restrict__ p, 
   const float4* m4 = reinterpret_cast<const float4*>(m + c.start);
   const float4* v4 = reinterpret_cast<const float4*>(v + c.start);
   uint2* s2 = shadow ? reinterpret_cast<uint2*>(shadow + c.start) : nullptr;
-  float4 P[kLambIter], M[kLambIter], V[kLambIter];
+  float4 P[kOptIter], M[kOptIter], V[kOptIter];
 #pragma unroll
-  for (int k = 0; k < kLambIter; ++k) {
+  for (int k = 0; k < kOptIter; ++k) {
     const int i = threadIdx.x + 256 * k;
     if (i < len4) {
       P[k] = p4[i];
@@ -241,7 +190,7 @@ __global__ __launch_bounds__(256) void lamb_apply_kernel(float* __restrict__ p, 
     }
   }
 #pragma unroll
-  for (int k = 0; k < kLambIter; ++k) {
+  for (int k = 0; k < kOptIter; ++k) {
     const int i = threadIdx.x + 256 * k;
     if (i < len4) {
       const float pa[4] = {P[k].x, P[k].y, P[k].z, P[k].w}, ma[4] = {M[k].x, M[k].y, M[k].z, M[k].w};
@@ -263,7 +212,7 @@ __global__ __launch_bounds__(256) void lamb_apply_kernel(float* __restrict__ p, 
   }
 }
 
-int lamb_chunk_elems() { return kLambChunk; }
+int lamb_chunk_elems() { return kOptChunk; }
 
 // p, g, m, v 16-byte aligned, shadow 8-byte aligned (checked by the binding); C chunks, T tensors;
 // tgroup (T,) tensor → group with hyper of 8 + 4 G floats, or null: every tensor in group 0

@@ -891,15 +891,17 @@ def text_mask(x, pad, state, unk, mask, p, lo, hi, advance=True):
 
 
 def sumsq(g, part):
-    """Σ g² as the kernel's partial buffer (csrc elementwise.hip sumsq_kernel): here one partial."""
+    """Σ g² as the kernel's partial buffer (csrc optim.hip sumsq_kernel): here one partial."""
     part.zero_()
     part[0] = (g.float() ** 2).sum()
 
 
-def adamw(p, g, m, v, shadow, hyper, eps, wd, clip, gscale, l2=False, zero_grad=False, loss_src=None, loss_ring=None,
-          norm_part=None):
-    lr, step, b1, b2 = float(hyper[0]), float(hyper[1]), float(hyper[3]), float(hyper[4])
-    if loss_src is not None:  # the step's loss into the engine's ring slot hyper[7]
+def _opt_prologue(hyper, clip, gscale, norm_part, loss_src, loss_ring):
+    """What every flat-space update starts with (csrc/optim_common.h opt_step): the step's loss into
+    the engine's ring slot ``hyper[7]``, then → (step, beta1, beta2, gs) with ``gs`` the factor of a
+    gradient element: ``gscale`` times the clip factor ``min(1, clip / (‖g‖·gscale + 1e-6))``."""
+    step, b1, b2 = float(hyper[1]), float(hyper[3]), float(hyper[4])
+    if loss_src is not None:
         loss_ring.view(-1)[int(float(hyper[7])) % loss_ring.numel()] = loss_src.reshape(())
     gs = gscale
     if clip > 0:
@@ -907,6 +909,11 @@ def adamw(p, g, m, v, shadow, hyper, eps, wd, clip, gscale, l2=False, zero_grad=
         f = clip / (norm + 1e-6)
         if f < 1:
             gs *= f
+    return step, b1, b2, gs
+
+
+def _adamw_range(p, g, m, v, shadow, lr, wd, eps, b1, b2, bc1, bc2, gs, l2, zero_grad):
+    """AdamW on one range of the flat buffers (views; ``shadow`` may be None)."""
     gg = g * gs
     if zero_grad:
         g.zero_()
@@ -916,11 +923,16 @@ def adamw(p, g, m, v, shadow, hyper, eps, wd, clip, gscale, l2=False, zero_grad=
         p.mul_(1 - lr * wd)
     m.mul_(b1).add_(gg, alpha=1 - b1)
     v.mul_(b2).addcmul_(gg, gg, value=1 - b2)
-    bc1, bc2 = 1 - b1 ** step, 1 - b2 ** step
     denom = (v.sqrt() / math.sqrt(bc2)).add_(eps)
     p.addcdiv_(m, denom, value=-lr / bc1)
     if shadow is not None:
         shadow.copy_(p.to(shadow.dtype))
+
+
+def adamw(p, g, m, v, shadow, hyper, eps, wd, clip, gscale, l2=False, zero_grad=False, loss_src=None, loss_ring=None,
+          norm_part=None):
+    step, b1, b2, gs = _opt_prologue(hyper, clip, gscale, norm_part, loss_src, loss_ring)
+    _adamw_range(p, g, m, v, shadow, float(hyper[0]), wd, eps, b1, b2, 1 - b1 ** step, 1 - b2 ** step, gs, l2, zero_grad)
 
 
 def _tensor_ranges(chunk_tab):
@@ -937,20 +949,12 @@ def _tensor_ranges(chunk_tab):
 
 def adamw_grouped(p, g, m, v, shadow, hyper, chunk_tab, tensor_group, groups, clip, gscale, l2=False, zero_grad=False,
                   loss_src=None, loss_ring=None, norm_part=None):
-    """AdamW with per-group lr / weight decay / eps, tensor by tensor (csrc/elementwise.hip
+    """AdamW with per-group lr / weight decay / eps, tensor by tensor (csrc/optim.hip
     adamw_grouped_kernel): tensor ``t`` takes ``hyper[8 + 4j : 8 + 4j + 3]`` of its group
     ``j = tensor_group[t]``; step, betas, the clip factor (the norm of all groups together),
     ``gscale``, ``l2`` and ``zero_grad`` are those of :func:`adamw`.  Padding between tensors belongs
     to no chunk and is left alone."""
-    step, b1, b2 = float(hyper[1]), float(hyper[3]), float(hyper[4])
-    if loss_src is not None:  # the step's loss into the engine's ring slot hyper[7]
-        loss_ring.view(-1)[int(float(hyper[7])) % loss_ring.numel()] = loss_src.reshape(())
-    gs = gscale
-    if clip > 0:
-        norm = math.sqrt(float(norm_part.sum())) * gscale  # norm of the mean (all-reduced sum × 1/world)
-        f = clip / (norm + 1e-6)
-        if f < 1:
-            gs *= f
+    step, b1, b2, gs = _opt_prologue(hyper, clip, gscale, norm_part, loss_src, loss_ring)
     bc1, bc2 = 1 - b1 ** step, 1 - b2 ** step
     hv, tg = hyper.tolist(), tensor_group.tolist()
     for t, lo, hi in _tensor_ranges(chunk_tab):
@@ -958,20 +962,8 @@ def adamw_grouped(p, g, m, v, shadow, hyper, chunk_tab, tensor_group, groups, cl
         if not 0 <= j < groups:
             raise ValueError(f"adamw_grouped: tensor {t} in group {j} of {groups}")
         lr, wd, eps = hv[8 + 4 * j:8 + 4 * j + 3]
-        w, gt, mt, vt = p[lo:hi], g[lo:hi], m[lo:hi], v[lo:hi]
-        gg = gt * gs
-        if zero_grad:
-            gt.zero_()
-        if l2:
-            gg = gg + wd * w
-        else:
-            w.mul_(1 - lr * wd)
-        mt.mul_(b1).add_(gg, alpha=1 - b1)
-        vt.mul_(b2).addcmul_(gg, gg, value=1 - b2)
-        denom = (vt.sqrt() / math.sqrt(bc2)).add_(eps)
-        w.addcdiv_(mt, denom, value=-lr / bc1)
-        if shadow is not None:
-            shadow[lo:hi].copy_(w.to(shadow.dtype))
+        _adamw_range(p[lo:hi], g[lo:hi], m[lo:hi], v[lo:hi], None if shadow is None else shadow[lo:hi], lr, wd, eps, b1,
+                     b2, bc1, bc2, gs, l2, zero_grad)
 
 
 def lamb(p, g, m, v, shadow, hyper, chunk_tab, tensor_tab, tensor_opt, partials, trust, eps, clip, gscale,
@@ -982,16 +974,9 @@ def lamb(p, g, m, v, shadow, hyper, chunk_tab, tensor_tab, tensor_opt, partials,
     no chunk and is left alone.  ``partials`` is the kernels' scratch: unused here.
     ``tensor_group`` (T,): tensor ``t`` takes its group's lr ``hyper[8 + 4·tensor_group[t]]``
     (None: every tensor group 0's, ``hyper[0]``)."""
-    lr, step, b1, b2 = float(hyper[0]), float(hyper[1]), float(hyper[3]), float(hyper[4])
+    lr = float(hyper[0])
     lrs = None if tensor_group is None else [float(hyper[8 + 4 * j]) for j in tensor_group.tolist()]
-    if loss_src is not None:  # the step's loss into the engine's ring slot hyper[7]
-        loss_ring.view(-1)[int(float(hyper[7])) % loss_ring.numel()] = loss_src.reshape(())
-    gs = gscale
-    if clip > 0:
-        norm = math.sqrt(float(norm_part.sum())) * gscale  # norm of the mean (all-reduced sum × 1/world)
-        f = clip / (norm + 1e-6)
-        if f < 1:
-            gs *= f
+    step, b1, b2, gs = _opt_prologue(hyper, clip, gscale, norm_part, loss_src, loss_ring)
     bc1, bc2s = 1 - b1 ** step, math.sqrt(1 - b2 ** step)
     chunks, tensors, opts = chunk_tab.tolist(), tensor_tab.tolist(), tensor_opt.tolist()
     for t, ((first, cnt), (wd, adapt)) in enumerate(zip(tensors, opts)):

@@ -22,12 +22,12 @@ parameter), so Lightning-layout checkpoints round-trip.  lr/betas/step live in a
 device tensor refreshed before each step, which keeps the update capturable in a hipGraph.
 With several parameter groups (at most 8; ``lr``, ``weight_decay`` and ``eps`` per group, equal
 ``betas``) that tensor carries 4 more words per group and the update is ``adamw_grouped`` over
-the chunk table of the flat buffer; one group runs the single-group kernel as before.
+the chunk table of the flat buffer (csrc/optim.hip); one group runs the single-group kernel.
 ``param_groups`` builds the usual groups (no decay on 1-d tensors, a prefix → lr multiplier map).
 
 ``Lamb`` / ``FusedLamb`` add LAMB: the flat space knows where tensors begin (``offsets``), so the
 fused update takes per-tensor trust ratios and per-tensor weight decay from chunk tables
-(``lamb_tables``, csrc/lamb.hip).
+(``lamb_tables``, csrc/lamb.hip; what the updates share on the device is csrc/optim_common.h).
 
 ``WeightEMA`` keeps an exponential moving average of the weights as one more flat fp32 buffer,
 updated by one launch behind the fused update and swapped in for evaluation (csrc/ema.hip).
@@ -46,7 +46,13 @@ ALIGN = 64  # elements; keeps every parameter view 256-byte aligned
 
 
 GRAD_REPLICAS = 8  # matches kGradReplicas in csrc/rowgemm.hip
-MAX_GROUPS = 8  # parameter groups of a fused optimizer; matches kAdamMaxGroups in csrc/elementwise.hip
+MAX_GROUPS = 8  # parameter groups of a fused optimizer; matches kOptMaxGroups in csrc/optim_common.h
+
+
+def _kernels(device):
+    """The module the flat-space updates are launched from: the HIP extension on the GPU (an error if it
+    is not built), its emulation on the CPU."""
+    return ext.require() if device.type == "cuda" else emulation
 
 
 class FlatParameterSpace:
@@ -101,8 +107,7 @@ class FlatParameterSpace:
         """grad[:n_rep] += Σ replicas; replicas ← 0 (no-op without replicated parameters)."""
         if self.grad_rep is None:
             return
-        K = ext.require() if self.device.type == "cuda" else emulation
-        K.fold_replicas(self.grad, self.grad_rep)
+        _kernels(self.device).fold_replicas(self.grad, self.grad_rep)
 
     def views(self, buf: torch.Tensor):
         return [buf[o:o + p.numel()].view(p.shape) for p, o in zip(self.params, self.offsets)]
@@ -231,10 +236,6 @@ class FusedAdamW(torch.optim.Optimizer):
             raise RuntimeError("attach_ema: attach before the step engine is built (per-bucket updates are already on)")
         self.ema = ema
 
-    def _ema_update(self, K):
-        if self.ema is not None:
-            K.ema_update(self.ema.avg, self.flat.data, self.hyper)
-
     # -- the update ---------------------------------------------------------------------
     def hyper_values(self):
         """lr / step / betas of the NEXT update (and the step engine's loss-ring slot; with an
@@ -275,40 +276,42 @@ class FusedAdamW(torch.optim.Optimizer):
         for this step."""
         if len(self.param_groups) > 1:
             raise NotImplementedError("range updates take one parameter group (a range knows no tensor boundaries)")
-        K = ext.require() if self.flat.device.type == "cuda" else emulation
         g = self.param_groups[0]
         f = self.flat
-        K.adamw(f.data[lo:hi], f.grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi],
-                None if f.shadow is None else f.shadow[lo:hi], self.hyper, g["eps"], g["weight_decay"], 0.0,
-                self.grad_scale, l2=self.l2, zero_grad=True)
+        _kernels(f.device).adamw(f.data[lo:hi], f.grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi],
+                                 None if f.shadow is None else f.shadow[lo:hi], self.hyper, g["eps"], g["weight_decay"],
+                                 0.0, self.grad_scale, l2=self.l2, zero_grad=True)
 
-    def device_update(self, zero_grad: bool = False, norm_staged: bool = False):
-        """The capturable part: (grad-norm) + fused AdamW kernel over the flat buffers.
+    def device_update(self, zero_grad: bool = False):
+        """The capturable part: fold, (grad-norm), the fused update over the flat buffers
+        (:meth:`_launch_update`), the EMA launch.
         ``zero_grad``: the kernel clears the gradient as it consumes it (flat buffers without
         replicas only; the step engine's captured step then skips its leading zero fill).
         In bucket mode the reducer has already updated every bucket: nothing to do."""
         if self.bucket_mode:
             return
-        K = ext.require() if self.flat.device.type == "cuda" else emulation
-        g = self.param_groups[0]
-        self.flat.fold()
+        f = self.flat
+        K = _kernels(f.device)
+        f.fold()
         if self.max_grad_norm > 0:
-            K.sumsq(self.flat.grad, self.norm_part)
+            K.sumsq(f.grad, self.norm_part)
         lo = self.loss_out
+        self._launch_update(K, zero_grad=zero_grad and f.grad_rep is None, loss_src=None if lo is None else lo[0],
+                            loss_ring=None if lo is None else lo[1], norm_part=self.norm_part)
+        if self.ema is not None:
+            K.ema_update(self.ema.avg, f.data, self.hyper)
+
+    def _launch_update(self, K, **common):
+        """The update itself: the single-group kernel, or ``adamw_grouped`` with several groups."""
+        f = self.flat
         if len(self.param_groups) > 1:
-            K.adamw_grouped(self.flat.data, self.flat.grad, self.exp_avg, self.exp_avg_sq, self.flat.shadow, self.hyper,
-                            self.chunk_tab, self.tensor_group, len(self.param_groups), self.max_grad_norm,
-                            self.grad_scale, l2=self.l2, zero_grad=zero_grad and self.flat.grad_rep is None,
-                            loss_src=None if lo is None else lo[0], loss_ring=None if lo is None else lo[1],
-                            norm_part=self.norm_part)
-            self._ema_update(K)
-            return
-        K.adamw(self.flat.data, self.flat.grad, self.exp_avg, self.exp_avg_sq, self.flat.shadow, self.hyper,
-                g["eps"], g["weight_decay"], self.max_grad_norm, self.grad_scale, l2=self.l2,
-                zero_grad=zero_grad and self.flat.grad_rep is None,
-                loss_src=None if lo is None else lo[0], loss_ring=None if lo is None else lo[1],
-                norm_part=self.norm_part)
-        self._ema_update(K)
+            K.adamw_grouped(f.data, f.grad, self.exp_avg, self.exp_avg_sq, f.shadow, self.hyper, self.chunk_tab,
+                            self.tensor_group, len(self.param_groups), self.max_grad_norm, self.grad_scale, l2=self.l2,
+                            **common)
+        else:
+            g = self.param_groups[0]
+            K.adamw(f.data, f.grad, self.exp_avg, self.exp_avg_sq, f.shadow, self.hyper, g["eps"], g["weight_decay"],
+                    self.max_grad_norm, self.grad_scale, l2=self.l2, **common)
 
     @torch.no_grad()
     def step(self, closure=None, staged: bool = False):
@@ -377,7 +380,7 @@ class FusedAdam(FusedAdamW):
         self.l2 = True
 
 
-LAMB_CHUNK = 4096  # elements per chunk of the LAMB tables; matches kLambChunk in csrc/lamb.hip
+LAMB_CHUNK = 4096  # elements per chunk of the chunk tables; matches kOptChunk in csrc/optim_common.h
 
 
 def _cut_chunks(offsets, numels):
@@ -558,20 +561,12 @@ class FusedLamb(FusedAdamW):
     def range_update(self, lo: int, hi: int):
         raise NotImplementedError("FusedLamb updates whole tensors (per-tensor trust ratios): no range updates")
 
-    def device_update(self, zero_grad: bool = False, norm_staged: bool = False):
-        """The capturable part: fold, (grad-norm), then the LAMB launches over the flat buffers."""
+    def _launch_update(self, K, **common):
+        """The LAMB launches over the flat buffers."""
         f = self.flat
-        K = ext.require() if f.device.type == "cuda" else emulation
-        f.fold()
-        if self.max_grad_norm > 0:
-            K.sumsq(f.grad, self.norm_part)
-        lo = self.loss_out
         K.lamb(f.data, f.grad, self.exp_avg, self.exp_avg_sq, f.shadow, self.hyper, self.chunk_tab, self.tensor_tab,
                self.tensor_opt, self.partials, self.trust, self.param_groups[0]["eps"], self.max_grad_norm,
-               self.grad_scale, zero_grad=zero_grad and f.grad_rep is None,
-               loss_src=None if lo is None else lo[0], loss_ring=None if lo is None else lo[1],
-               norm_part=self.norm_part, tensor_group=self.tensor_group)
-        self._ema_update(K)
+               self.grad_scale, tensor_group=self.tensor_group, **common)
 
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
@@ -648,11 +643,10 @@ class WeightEMA:
         if omd == 0.0:
             return
         if self.flat is not None:
-            K = ext.require() if self.flat.device.type == "cuda" else emulation
             if self._hyper is None:
                 self._hyper = torch.zeros(8, dtype=torch.float32, device=self.flat.device)
             self._hyper[5] = omd
-            K.ema_update(self.avg, self.flat.data, self._hyper)
+            _kernels(self.flat.device).ema_update(self.avg, self.flat.data, self._hyper)
             return
         for p, a in zip(self.params, self._avgs):
             if omd == 1.0:
@@ -670,8 +664,7 @@ class WeightEMA:
         weight-cache entries bound to the flat shadow — rewritten by the same launch — follow."""
         if self.flat is not None:
             f = self.flat
-            K = ext.require() if f.device.type == "cuda" else emulation
-            K.ema_swap(f.data, self.avg, f.shadow)
+            _kernels(f.device).ema_swap(f.data, self.avg, f.shadow)
             from .fused import weight_cache
 
             shadows = f.views(f.shadow) if f.shadow is not None else [None] * len(f.params)

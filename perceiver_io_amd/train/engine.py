@@ -308,7 +308,7 @@ class StepEngine:
                     opt.loss_out = (lv if lv.dtype == torch.float32 else lv.float(), self._loss_ring)
                 # every replay of this graph is preceded by a staging of the hyper-parameters
                 # (_stage), which also zeroes the gradient-norm accumulator
-                opt.device_update(zero_grad=self._self_zeroing, norm_staged=True)
+                opt.device_update(zero_grad=self._self_zeroing)
                 opt.loss_out = None
             return loss
 

@@ -5,6 +5,8 @@ import os
 import pytest
 import torch
 
+from optim_cases import close
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
@@ -14,22 +16,6 @@ def _ext():
     from perceiver_io_amd.ops import ext
 
     return ext.require()
-
-
-def close(a, b, rel, name=""):
-    """tests/test_kernels_gpu.py ``close`` (the AdamW kernel check runs it with rel = 1e-5):
-    relative Frobenius error and max-abs error against the reference's largest value."""
-    a, b = a.float().cpu(), b.float().cpu()
-    assert a.shape == b.shape, (name, a.shape, b.shape)
-    fin = torch.isfinite(b)
-    assert torch.equal(torch.isfinite(a), fin), f"{name}: non-finite pattern differs"
-    a, b = a[fin], b[fin]
-    fro = ((a.double() - b.double()).norm() / (b.double().norm() + 1e-30)).item()
-    scale = b.abs().max().item() + 1e-6
-    err = (a - b).abs().max().item()
-    print(f"{name}: rel fro {fro:.3e}, max err {err:.3e} (scale {scale:.3e})")
-    assert fro <= min(rel, 1e-2), f"{name}: relative Frobenius error {fro:.3e}"
-    assert err <= rel * scale, f"{name}: max err {err:.3e} vs scale {scale:.3e}"
 
 
 def _case():

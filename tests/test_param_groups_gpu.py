@@ -1,4 +1,4 @@
-"""Parameter groups on the GPU: the ``adamw_grouped`` kernel (csrc/elementwise.hip) against its
+"""Parameter groups on the GPU: the ``adamw_grouped`` kernel (csrc/optim.hip) against its
 emulation and, bit for bit, against the single-group ``adamw`` launch; ``lamb`` with a tensor → group
 table; a captured step that reads the group words on the device; the checked build."""
 import os
@@ -8,10 +8,12 @@ import sys
 import pytest
 import torch
 
+from optim_cases import NUMELS, close
+from optim_cases import flat_case as _case
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-NUMELS = [1, 3, 5, 63, 64, 65, 4095, 4096, 4097, 8193]
 # (lr, weight decay, eps) per group; tensor t sits in group t % G
 GROUP_OPTS = [(2e-3, 0.01, 1e-8), (5e-4, 0.0, 1e-8), (1e-3, 0.1, 1e-6), (3e-3, 0.05, 1e-7)]
 GSCALE = 0.5
@@ -22,47 +24,6 @@ def _ext():
     from perceiver_io_amd.ops import ext
 
     return ext.require()
-
-
-def close(a, b, rel, name=""):
-    """tests/test_lamb_gpu.py ``close`` (the AdamW kernel check runs it with rel = 1e-5): relative
-    Frobenius error and max-abs error against the reference's largest value."""
-    a, b = a.float().cpu(), b.float().cpu()
-    assert a.shape == b.shape, (name, a.shape, b.shape)
-    fin = torch.isfinite(b)
-    assert torch.equal(torch.isfinite(a), fin), f"{name}: non-finite pattern differs"
-    a, b = a[fin], b[fin]
-    fro = ((a.double() - b.double()).norm() / (b.double().norm() + 1e-30)).item()
-    scale = b.abs().max().item() + 1e-6
-    err = (a - b).abs().max().item()
-    print(f"{name}: rel fro {fro:.3e}, max err {err:.3e} (scale {scale:.3e})")
-    assert fro <= min(rel, 1e-2), f"{name}: relative Frobenius error {fro:.3e}"
-    assert err <= rel * scale, f"{name}: max err {err:.3e} vs scale {scale:.3e}"
-
-
-def _case():
-    """One flat buffer of the tensor sizes above (64-element alignment); the padding of m and v
-    is NaN, that of p and g zero."""
-    from perceiver_io_amd.ops.optim import ALIGN, lamb_tables
-
-    offsets, off = [], 0
-    for n in NUMELS:
-        offsets.append(off)
-        off += (n + ALIGN - 1) // ALIGN * ALIGN
-    g = torch.Generator().manual_seed(23)
-    valid = torch.zeros(off, dtype=torch.bool)
-    for o, n in zip(offsets, NUMELS):
-        valid[o:o + n] = True
-    zero, nan = torch.zeros(off), torch.full((off,), float("nan"))
-    p = torch.where(valid, torch.randn(off, generator=g), zero)
-    grad = torch.where(valid, torch.randn(off, generator=g), zero)
-    m = torch.where(valid, torch.randn(off, generator=g) * 0.1, nan)
-    v = torch.where(valid, torch.rand(off, generator=g) * 0.01, nan)
-    T = len(NUMELS)
-    chunk_tab, tensor_tab, tensor_opt = lamb_tables(offsets, NUMELS, [0.01, 0.0] * (T // 2), [True, False] * (T // 2), DEV)
-    assert chunk_tab.shape[0] > T and off % 4 == 0
-    return dict(offsets=offsets, valid=valid.to(DEV), p=p.to(DEV), g=grad.to(DEV), m=m.to(DEV), v=v.to(DEV),
-                chunk_tab=chunk_tab, tensor_tab=tensor_tab, tensor_opt=tensor_opt)
 
 
 @pytest.fixture(scope="module")
