@@ -28,7 +28,7 @@ int64_t check_errors(bool reset) {
                    pio::check_errors_mlm_head(reset) | pio::check_errors_ce_head(reset) | pio::check_errors_topk_head(reset) |
                    pio::check_errors_rowgemm(reset) | pio::check_errors_pixel_head(reset) |
                    pio::check_errors_soft_ce_head(reset) | pio::check_errors_augment(reset) |
-                   pio::check_errors_randaugment(reset));
+                   pio::check_errors_randaugment(reset) | pio::check_errors_health(reset));
 }
 bool checked_build() { return PIO_CHECKS != 0; }
 // checked builds, outside graph capture: wait for the kernel just launched and raise on any
@@ -1894,6 +1894,15 @@ const float* norm_part_arg(const char* fn, double clip, const OptT& norm_part) {
   return norm_part->data_ptr<float>();
 }
 
+// the step guard's words (optim_common.h): 8 fp32 on the device, 16-byte aligned; absent = off
+const float* guard_arg(const char* fn, const OptT& guard) {
+  if (!guard.has_value()) return nullptr;
+  TORCH_CHECK(guard->is_cuda() && guard->scalar_type() == torch::kFloat32 && guard->is_contiguous() &&
+                  guard->numel() >= 8 && aligned(guard->data_ptr(), 16),
+              fn, ": guard must be a contiguous, 16-byte aligned fp32 GPU tensor of 8 words");
+  return guard->data_ptr<float>();
+}
+
 // chunk_tab (C, 3) int64 = (start, length, tensor) → its pointer; C fits an int
 const long long* chunk_tab_arg(const char* fn, const Tensor& chunk_tab) {
   TORCH_CHECK(chunk_tab.is_cuda() && chunk_tab.scalar_type() == torch::kInt64 && chunk_tab.dim() == 2 &&
@@ -1912,11 +1921,12 @@ const int* tensor_group_arg(const char* fn, const Tensor& tensor_group, int64_t 
 }  // namespace
 
 void adamw(Tensor p, Tensor g, Tensor m, Tensor v, OptT shadow, Tensor hyper, double eps, double wd, double clip,
-           double gscale, bool l2, bool zero_grad, OptT loss_src, OptT loss_ring, OptT norm_part) {
+           double gscale, bool l2, bool zero_grad, OptT loss_src, OptT loss_ring, OptT norm_part, OptT guard) {
   const FlatBufs b = flat_bufs("adamw", p, g, m, v, shadow, hyper, false);
   const LossRing lr = loss_ring_args("adamw", loss_src, loss_ring);
   pio::adamw_launch(b.p, b.g, b.m, b.v, b.shadow, b.n, b.hyper, (float)eps, (float)wd, (float)clip, (float)gscale,
-                    l2 ? 1 : 0, zero_grad ? 1 : 0, lr.src, lr.ring, lr.n, norm_part_arg("adamw", clip, norm_part), stream());
+                    l2 ? 1 : 0, zero_grad ? 1 : 0, lr.src, lr.ring, lr.n, norm_part_arg("adamw", clip, norm_part),
+                    guard_arg("adamw", guard), stream());
 }
 
 // fused LAMB over the flat buffers (csrc/lamb.hip): chunk_tab (C, 3) int64 = (start, length, tensor),
@@ -1924,7 +1934,7 @@ void adamw(Tensor p, Tensor g, Tensor m, Tensor v, OptT shadow, Tensor hyper, do
 // partials: >= 2 C fp32 (per-chunk Σw², Σu²), trust: (T,) fp32 (written every step, kept)
 void lamb(Tensor p, Tensor g, Tensor m, Tensor v, OptT shadow, Tensor hyper, Tensor chunk_tab, Tensor tensor_tab,
           Tensor tensor_opt, Tensor partials, Tensor trust, double eps, double clip, double gscale, bool zero_grad,
-          OptT loss_src, OptT loss_ring, OptT norm_part, OptT tensor_group) {
+          OptT loss_src, OptT loss_ring, OptT norm_part, OptT tensor_group, OptT guard) {
   const FlatBufs b = flat_bufs("lamb", p, g, m, v, shadow, hyper, true);
   const LossRing lr = loss_ring_args("lamb", loss_src, loss_ring);
   const long long* chunks = chunk_tab_arg("lamb", chunk_tab);
@@ -1948,7 +1958,8 @@ void lamb(Tensor p, Tensor g, Tensor m, Tensor v, OptT shadow, Tensor hyper, Ten
   }
   pio::lamb_launch(b.p, b.g, b.m, b.v, b.shadow, b.n, b.hyper, chunks, C, tensor_tab.data_ptr<int>(), f32p(tensor_opt),
                    (int)T, partials.data_ptr<float>(), trust.data_ptr<float>(), (float)eps, (float)clip, (float)gscale,
-                   zero_grad ? 1 : 0, lr.src, lr.ring, lr.n, norm_part_arg("lamb", clip, norm_part), tg, G, stream());
+                   zero_grad ? 1 : 0, lr.src, lr.ring, lr.n, norm_part_arg("lamb", clip, norm_part), tg, G,
+                   guard_arg("lamb", guard), stream());
 }
 
 // AdamW with per-group lr / weight decay / eps (optim.hip adamw_grouped_kernel): chunk_tab (C, 3)
@@ -1956,7 +1967,7 @@ void lamb(Tensor p, Tensor g, Tensor m, Tensor v, OptT shadow, Tensor hyper, Ten
 // group (lr, weight decay, eps, reserved)
 void adamw_grouped(Tensor p, Tensor g, Tensor m, Tensor v, OptT shadow, Tensor hyper, Tensor chunk_tab,
                    Tensor tensor_group, int64_t groups, double clip, double gscale, bool l2, bool zero_grad, OptT loss_src,
-                   OptT loss_ring, OptT norm_part) {
+                   OptT loss_ring, OptT norm_part, OptT guard) {
   const FlatBufs b = flat_bufs("adamw_grouped", p, g, m, v, shadow, hyper, true);
   const LossRing lr = loss_ring_args("adamw_grouped", loss_src, loss_ring);
   const long long* chunks = chunk_tab_arg("adamw_grouped", chunk_tab);
@@ -1966,7 +1977,51 @@ void adamw_grouped(Tensor p, Tensor g, Tensor m, Tensor v, OptT shadow, Tensor h
               "adamw_grouped: 1 <= groups <= 8 and hyper of 8 + 4 * groups floats");
   TORCH_CHECK(pio::adamw_grouped_launch(b.p, b.g, b.m, b.v, b.shadow, b.n, b.hyper, chunks, chunk_tab.size(0), tg, (int)T,
                                         (int)groups, (float)clip, (float)gscale, l2 ? 1 : 0, zero_grad ? 1 : 0, lr.src,
-                                        lr.ring, lr.n, norm_part_arg("adamw_grouped", clip, norm_part), stream()) == 0);
+                                        lr.ring, lr.n, norm_part_arg("adamw_grouped", clip, norm_part),
+                                        guard_arg("adamw_grouped", guard), stream()) == 0);
+}
+
+// the step guard (csrc/health.hip step_guard_kernel): from sumsq's partials and hyper[1] to the 8 guard
+// words (read and rewritten: the counters live in them)
+void step_guard(Tensor part, Tensor hyper, Tensor guard, double gscale) {
+  CHECK_CUDA(part); CHECK_CUDA(hyper); CHECK_DT(part, torch::kFloat32); CHECK_DT(hyper, torch::kFloat32);
+  TORCH_CHECK(part.is_contiguous() && part.numel() >= kSumsqParts && hyper.is_contiguous() && hyper.numel() >= 8,
+              "step_guard: the sumsq partials (>= 512 floats) and hyper (>= 8 floats), contiguous");
+  const float* gp = guard_arg("step_guard", guard);
+  TORCH_CHECK(part.get_device() == hyper.get_device() && part.get_device() == guard.get_device(),
+              "step_guard: part, hyper and guard on one device");
+  pio::step_guard_launch(f32p(part), f32p(hyper), const_cast<float*>(gp), (float)gscale, stream());
+}
+
+// per-tensor statistics of the flat gradient and weights (csrc/health.hip): stats (T, 4) fp32 =
+// ‖g‖·gscale, ‖w‖, max|g|·gscale, non-finite gradient elements, written when hyper[6] != 0; with a guard
+// that flags this step the same rows go to skip_stats.  part: >= 4 C fp32 of scratch.
+void tensor_stats(Tensor g, Tensor w, Tensor hyper, Tensor chunk_tab, Tensor tensor_tab, Tensor part, Tensor stats,
+                  double gscale, OptT guard, OptT skip_stats) {
+  for (const Tensor* t : {&g, &w, &hyper, &part, &stats})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kFloat32 && t->is_contiguous(),
+                "tensor_stats: g, w, hyper, part and stats must be contiguous fp32 GPU tensors");
+  const long long* chunks = chunk_tab_arg("tensor_stats", chunk_tab);
+  CHECK_CUDA(tensor_tab); CHECK_DT(tensor_tab, torch::kInt32);
+  const int64_t C = chunk_tab.size(0), T = tensor_tab.size(0);
+  TORCH_CHECK(tensor_tab.dim() == 2 && tensor_tab.size(1) == 2 && tensor_tab.is_contiguous() && T < (int64_t(1) << 31),
+              "tensor_stats: tensor_tab (T, 2) int32, contiguous");
+  TORCH_CHECK(g.numel() == w.numel() && hyper.numel() >= 8 && part.numel() >= 4 * C && stats.numel() >= 4 * T,
+              "tensor_stats: g and w of one size, hyper >= 8, part >= 4 C and stats >= 4 T floats");
+  TORCH_CHECK(guard.has_value() == skip_stats.has_value(), "tensor_stats: guard and skip_stats go together");
+  float* sp = nullptr;
+  if (skip_stats.has_value()) {
+    TORCH_CHECK(skip_stats->is_cuda() && skip_stats->scalar_type() == torch::kFloat32 && skip_stats->is_contiguous() &&
+                    skip_stats->numel() >= 4 * T && skip_stats->data_ptr() != stats.data_ptr(),
+                "tensor_stats: skip_stats must be a second contiguous fp32 GPU tensor of >= 4 T floats");
+    sp = skip_stats->data_ptr<float>();
+  }
+  TORCH_CHECK(aligned(g.data_ptr(), 16) && aligned(w.data_ptr(), 16) && aligned(part.data_ptr(), 16) &&
+                  aligned(stats.data_ptr(), 16) && aligned(sp, 16),
+              "tensor_stats: the buffers must be 16-byte aligned");
+  pio::tensor_stats_launch(f32p(g), f32p(w), g.numel(), f32p(hyper), guard_arg("tensor_stats", guard), chunks, C,
+                           tensor_tab.data_ptr<int>(), (int)T, (float)gscale, part.data_ptr<float>(),
+                           stats.data_ptr<float>(), sp, stream());
 }
 
 // weight EMA over a flat fp32 buffer (csrc/ema.hip): ema ← ema + hyper[5]·(w − ema); hyper[5] = 0
@@ -2435,16 +2490,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adamw", &adamw, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("shadow"), py::arg("hyper"),
         py::arg("eps"), py::arg("wd"), py::arg("clip"), py::arg("gscale"), py::arg("l2") = false,
         py::arg("zero_grad") = false, py::arg("loss_src") = py::none(), py::arg("loss_ring") = py::none(),
-        py::arg("norm_part") = py::none());
+        py::arg("norm_part") = py::none(), py::arg("guard") = py::none());
   m.def("lamb", &lamb, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("shadow"), py::arg("hyper"),
         py::arg("chunk_tab"), py::arg("tensor_tab"), py::arg("tensor_opt"), py::arg("partials"), py::arg("trust"),
         py::arg("eps"), py::arg("clip"), py::arg("gscale"), py::arg("zero_grad") = false,
         py::arg("loss_src") = py::none(), py::arg("loss_ring") = py::none(), py::arg("norm_part") = py::none(),
-        py::arg("tensor_group") = py::none());
+        py::arg("tensor_group") = py::none(), py::arg("guard") = py::none());
   m.def("adamw_grouped", &adamw_grouped, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("shadow"),
         py::arg("hyper"), py::arg("chunk_tab"), py::arg("tensor_group"), py::arg("groups"), py::arg("clip"),
         py::arg("gscale"), py::arg("l2") = false, py::arg("zero_grad") = false, py::arg("loss_src") = py::none(),
-        py::arg("loss_ring") = py::none(), py::arg("norm_part") = py::none());
+        py::arg("loss_ring") = py::none(), py::arg("norm_part") = py::none(), py::arg("guard") = py::none());
+  m.def("step_guard", &step_guard, py::arg("part"), py::arg("hyper"), py::arg("guard"), py::arg("gscale"));
+  m.def("tensor_stats", &tensor_stats, py::arg("g"), py::arg("w"), py::arg("hyper"), py::arg("chunk_tab"),
+        py::arg("tensor_tab"), py::arg("part"), py::arg("stats"), py::arg("gscale"), py::arg("guard") = py::none(),
+        py::arg("skip_stats") = py::none());
   m.attr("LAMB_CHUNK") = pio::lamb_chunk_elems();
   m.def("ema_update", &ema_update, py::arg("ema"), py::arg("w"), py::arg("hyper"));
   m.def("ema_swap", &ema_swap, py::arg("w"), py::arg("ema"), py::arg("shadow") = py::none());

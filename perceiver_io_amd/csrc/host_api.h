@@ -352,15 +352,29 @@ long long ema_pass_elems();
 void ema_update_launch(float* ema, const float* w, long long n, const float* hyper, hipStream_t st);
 // w ↔ ema in place, shadow (may be null) ← bf16(new w); 16-byte aligned (shadow 8), n % 4 == 0
 void ema_swap_launch(float* w, float* ema, uint16_t* shadow, long long n, hipStream_t st);
+// ---- health.hip ----
+// the step guard (optim_common.h: the 8 guard words): judges Σ g² of sumsq's partials, one workgroup.
+// guard: kGuardWords fp32, part: kSumsqBlocks fp32
+void step_guard_launch(const float* part, const float* hyper, float* guard, float gscale, hipStream_t st);
+// per-tensor gradient / weight statistics over the chunk table, when hyper[6] != 0 (→ stats) or the
+// guard flags this step (→ skip_stats; guard and skip_stats may be null together): part (C, 4) fp32
+// scratch, tensors (T, 2) int32 = (first chunk, chunks), stats / skip_stats (T, 4) fp32 =
+// ‖g‖·gscale, ‖w‖, max|g|·gscale, non-finite gradient elements.  g, w 16-byte aligned.
+void tensor_stats_launch(const float* g, const float* w, long long n, const float* hyper, const float* guard,
+                         const long long* chunks, long long C, const int* tensors, int T, float gscale, float* part,
+                         float* stats, float* skip_stats, hipStream_t st);
+unsigned check_errors_health(bool reset);
 // ---- lamb.hip ----
 // elements per chunk of the chunk table (lamb_launch, adamw_grouped_launch): the extension's LAMB_CHUNK
 int lamb_chunk_elems();
 // p, g, m, v 16-byte aligned, shadow 8-byte aligned (checked by the binding); C chunks, T tensors;
-// tgroup (T,) tensor → group with hyper of 8 + 4 G floats, or null: every tensor in group 0
+// tgroup (T,) tensor → group with hyper of 8 + 4 G floats, or null: every tensor in group 0;
+// guard: the step guard's words or null
 void lamb_launch(float* p, float* g, float* m, float* v, uint16_t* shadow, long long n, const float* hyper,
                  const long long* chunks, long long C, const int* tensors, const float* topt, int T, float* partials,
                  float* trust, float eps, float clip, float gscale, int zero_g, const float* loss_src,
-                 float* loss_ring, int ring_n, const float* norm_part, const int* tgroup, int G, hipStream_t st);
+                 float* loss_ring, int ring_n, const float* norm_part, const int* tgroup, int G, const float* guard,
+                 hipStream_t st);
 // ---- mlm_head.hip ----
 void mlm_select_launch(const int64_t* labels, int B, int L, int cap, int gcap, int64_t* idx_b, int64_t* lab_b,
                        int* count, int64_t* gidx, int64_t* glab, float* total, bool* overflow, bool* sticky,
@@ -382,13 +396,13 @@ unsigned check_errors_mlm_head(bool reset);
 void sumsq_launch(const float* g, long long n, float* part, hipStream_t st);
 void adamw_launch(float* p, float* g, float* m, float* v, uint16_t* shadow, long long n, const float* hyper,
                   float eps, float wd, float clip, float gscale, int l2, int zero_g, const float* loss_src,
-                  float* loss_ring, int ring_n, const float* norm_part, hipStream_t st);
+                  float* loss_ring, int ring_n, const float* norm_part, const float* guard, hipStream_t st);
 // AdamW with per-group lr / weight decay / eps over the LAMB chunk table (chunks (C, 3) int64,
 // tgroup (T,) int32 = tensor → group, hyper of 8 + 4 G floats); -1 for G outside [1, 8]
 int adamw_grouped_launch(float* p, float* g, float* m, float* v, uint16_t* shadow, long long n, const float* hyper,
                          const long long* chunks, long long C, const int* tgroup, int T, int G, float clip, float gscale,
                          int l2, int zero_g, const float* loss_src, float* loss_ring, int ring_n,
-                         const float* norm_part, hipStream_t st);
+                         const float* norm_part, const float* guard, hipStream_t st);
 void fold_replicas_launch(float* grad, float* rep, long long n, int nrep, hipStream_t st);
 unsigned check_errors_optim(bool reset);
 // ---- pe_proj.hip ----

@@ -44,15 +44,24 @@ __device__ __forceinline__ void block_sum2(float& a, float& b) {
   b = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
 }
 
-// pass 1.  hyper / loss_src / loss_ring / zero_g / clip as in adamw_kernel (optim.hip)
+// pass 1.  hyper / loss_src / loss_ring / zero_g / clip / guard as in adamw_kernel (optim.hip)
 __global__ __launch_bounds__(256) void lamb_moments_kernel(
     const float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long long n,
     const float* __restrict__ hyper, const long long* __restrict__ chunks, const float* __restrict__ topt, int T,
     float* __restrict__ partials, float eps, float clip, float gscale, int zero_g, const float* __restrict__ loss_src,
-    float* __restrict__ loss_ring, int ring_n, const float* __restrict__ norm_part) {
-  const OptStep s = opt_step(hyper, clip, gscale, loss_src, loss_ring, ring_n, norm_part);
-  const float bc1 = lamb_bias_correction(s.beta1, s.step), bc2s = sqrtf(lamb_bias_correction(s.beta2, s.step));
+    float* __restrict__ loss_ring, int ring_n, const float* __restrict__ norm_part, const float* __restrict__ guard) {
+  const OptStep s = opt_step(hyper, clip, gscale, loss_src, loss_ring, ring_n, norm_part, guard);
   const OptChunk c = opt_chunk(chunks, blockIdx.x, n, T);
+  if (s.skip) {  // uniform over the launch: the gradient is cleared, m, v and the partials stay
+    if (zero_g && c.ok) {
+      float4* gz = reinterpret_cast<float4*>(g + c.start);
+      for (int i = threadIdx.x; i < (c.len >> 2); i += 256) gz[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      const int t = (c.len & ~3) + threadIdx.x;
+      if (t < c.len) g[c.start + t] = 0.f;
+    }
+    return;
+  }
+  const float bc1 = lamb_bias_correction(s.beta1, s.step), bc2s = sqrtf(lamb_bias_correction(s.beta2, s.step));
   float sw = 0.f, su = 0.f;
   if (c.ok) {
     const float wd = topt[2 * c.tid];
@@ -119,8 +128,10 @@ __global__ __launch_bounds__(256) void lamb_moments_kernel(
 __global__ __launch_bounds__(256) void lamb_trust_kernel(const float* __restrict__ partials,
                                                          const int* __restrict__ tensors,
                                                          const float* __restrict__ topt, long long C,
-                                                         float* __restrict__ trust) {
+                                                         float* __restrict__ trust,
+                                                         const float* __restrict__ guard) {
   __shared__ double red[2][256];
+  if (opt_guard_skip(guard)) return;  // a skipped step keeps the last update's trust ratios
   const int t = blockIdx.x;
   const long long first = tensors[2 * t], cnt = tensors[2 * t + 1];
   const bool adapt = topt[2 * t + 1] != 0.f && first >= 0 && cnt >= 0 && first + cnt <= C;
@@ -156,8 +167,10 @@ __global__ __launch_bounds__(256) void lamb_apply_kernel(float* __restrict__ p, 
                                                          const long long* __restrict__ chunks,
                                                          const float* __restrict__ topt, int T,
                                                          const float* __restrict__ trust, float eps,
-                                                         const int* __restrict__ tgroup, int G) {
-  const float step = hyper[1], beta1 = hyper[3], beta2 = hyper[4];
+                                                         const int* __restrict__ tgroup, int G,
+                                                         const float* __restrict__ guard) {
+  if (opt_guard_skip(guard)) return;  // the same word the other two launches of this step read
+  const float step = opt_guard_step(hyper, guard), beta1 = hyper[3], beta2 = hyper[4];
   const float bc1 = lamb_bias_correction(beta1, step), bc2s = sqrtf(lamb_bias_correction(beta2, step));
   const OptChunk c = opt_chunk(chunks, blockIdx.x, n, T);
   if (!c.ok) return;
@@ -219,13 +232,14 @@ int lamb_chunk_elems() { return kOptChunk; }
 void lamb_launch(float* p, float* g, float* m, float* v, uint16_t* shadow, long long n, const float* hyper,
                  const long long* chunks, long long C, const int* tensors, const float* topt, int T, float* partials,
                  float* trust, float eps, float clip, float gscale, int zero_g, const float* loss_src,
-                 float* loss_ring, int ring_n, const float* norm_part, const int* tgroup, int G, hipStream_t st) {
+                 float* loss_ring, int ring_n, const float* norm_part, const int* tgroup, int G, const float* guard,
+                 hipStream_t st) {
   if (C <= 0 || T <= 0) return;
   hipLaunchKernelGGL(lamb_moments_kernel, dim3((unsigned)C), dim3(256), 0, st, p, g, m, v, n, hyper, chunks, topt, T,
-                     partials, eps, clip, gscale, zero_g, loss_src, loss_ring, ring_n, norm_part);
-  hipLaunchKernelGGL(lamb_trust_kernel, dim3((unsigned)T), dim3(256), 0, st, partials, tensors, topt, C, trust);
+                     partials, eps, clip, gscale, zero_g, loss_src, loss_ring, ring_n, norm_part, guard);
+  hipLaunchKernelGGL(lamb_trust_kernel, dim3((unsigned)T), dim3(256), 0, st, partials, tensors, topt, C, trust, guard);
   hipLaunchKernelGGL(lamb_apply_kernel, dim3((unsigned)C), dim3(256), 0, st, p, m, v, shadow, n, hyper, chunks, topt, T,
-                     trust, eps, tgroup, G);
+                     trust, eps, tgroup, G, guard);
 }
 
 }  // namespace pio

@@ -51,23 +51,35 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g,
 // adamw_elem that do not depend on the parameter group
 struct AdamStep {
   float gs, beta1, omb1, beta2, omb2, bc1, bc2s;
+  bool skip;  // the step guard flags this step: clear the gradient (zero_g), touch nothing else
 };
 __device__ __forceinline__ AdamStep adam_step(const float* __restrict__ hyper, float clip, float gscale,
                                               const float* __restrict__ loss_src, float* __restrict__ loss_ring,
-                                              int ring_n, const float* __restrict__ norm_part) {
-  const OptStep s = opt_step(hyper, clip, gscale, loss_src, loss_ring, ring_n, norm_part);
+                                              int ring_n, const float* __restrict__ norm_part,
+                                              const float* __restrict__ guard) {
+  const OptStep s = opt_step(hyper, clip, gscale, loss_src, loss_ring, ring_n, norm_part, guard);
   return AdamStep{s.gs, s.beta1, 1.f - s.beta1, s.beta2, 1.f - s.beta2, 1.f - powf(s.beta1, s.step),
-                  sqrtf(1.f - powf(s.beta2, s.step))};
+                  sqrtf(1.f - powf(s.beta2, s.step)), s.skip};
 }
 
 // zero_g: the gradient is cleared as it is consumed (a replayed step then needs no separate
 // zero fill of the flat gradient buffer before its backward)
+// guard (null = off): the step guard's words (optim_common.h).  On a step it flags, the loss still
+// reaches the ring and the gradient is still cleared (zero_g) — the poison must not stay in the
+// accumulator for the next backward — while p, m, v and the shadow are left as they are; on the other
+// steps the bias corrections take the guard's effective step.
 __global__ void adamw_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                              float* __restrict__ v, uint16_t* __restrict__ shadow, long long n,
                              const float* __restrict__ hyper, float eps, float wd, float clip, float gscale,
                              int l2, int zero_g, const float* __restrict__ loss_src, float* __restrict__ loss_ring,
-                             int ring_n, const float* __restrict__ norm_part) {
-  const AdamStep s = adam_step(hyper, clip, gscale, loss_src, loss_ring, ring_n, norm_part);
+                             int ring_n, const float* __restrict__ norm_part, const float* __restrict__ guard) {
+  const AdamStep s = adam_step(hyper, clip, gscale, loss_src, loss_ring, ring_n, norm_part, guard);
+  if (s.skip) {  // uniform over the launch
+    if (zero_g)
+      for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+        g[i] = 0.f;
+    return;
+  }
   const float lr = hyper[0], step_size = lr / s.bc1, decay = fmaf(-wd, lr, 1.f);
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
     const float g0 = g[i];
@@ -91,8 +103,15 @@ __global__ __launch_bounds__(256) void adamw4_kernel(float4* __restrict__ p, flo
                                                      const float* __restrict__ hyper, float eps, float wd, float clip,
                                                      float gscale, int l2, int zero_g, const float* __restrict__ loss_src,
                                                      float* __restrict__ loss_ring, int ring_n,
-                                                     const float* __restrict__ norm_part) {
-  const AdamStep s = adam_step(hyper, clip, gscale, loss_src, loss_ring, ring_n, norm_part);
+                                                     const float* __restrict__ norm_part,
+                                                     const float* __restrict__ guard) {
+  const AdamStep s = adam_step(hyper, clip, gscale, loss_src, loss_ring, ring_n, norm_part, guard);
+  if (s.skip) {  // uniform over the launch
+    if (zero_g)
+      for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x)
+        g[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    return;
+  }
   const float lr = hyper[0], step_size = lr / s.bc1, decay = fmaf(-wd, lr, 1.f);
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
     const float4 p4 = p[i], g4 = g[i], m4 = m[i], v4 = v[i];
@@ -122,13 +141,22 @@ __global__ __launch_bounds__(256) void adamw_grouped_kernel(
     float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
     uint16_t* __restrict__ shadow, long long n, const float* __restrict__ hyper, const long long* __restrict__ chunks,
     long long C, const int* __restrict__ tgroup, int T, int G, float clip, float gscale, int l2, int zero_g,
-    const float* __restrict__ loss_src, float* __restrict__ loss_ring, int ring_n, const float* __restrict__ norm_part) {
-  const AdamStep s = adam_step(hyper, clip, gscale, loss_src, loss_ring, ring_n, norm_part);
+    const float* __restrict__ loss_src, float* __restrict__ loss_ring, int ring_n, const float* __restrict__ norm_part,
+    const float* __restrict__ guard) {
+  const AdamStep s = adam_step(hyper, clip, gscale, loss_src, loss_ring, ring_n, norm_part, guard);
+  if (s.skip && !zero_g) return;  // uniform over the launch
   for (long long c = blockIdx.x; c < C; c += gridDim.x) {  // uniform over the block
     const OptChunk k = opt_chunk(chunks, c, n, T);
     const int grp = k.ok ? tgroup[k.tid] : -1;
     if (grp < 0 || grp >= G) {
       if (threadIdx.x == 0) pio_flag(kErrOptTable);
+      continue;
+    }
+    if (s.skip) {  // a skipped step: the chunk's gradient is cleared, nothing else of it is touched
+      float4* gz = reinterpret_cast<float4*>(g + k.start);
+      for (int i = threadIdx.x; i < (k.len >> 2); i += 256) gz[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      const int t = (k.len & ~3) + threadIdx.x;
+      if (t < k.len) g[k.start + t] = 0.f;
       continue;
     }
     const float* hg = hyper + kOptGroupBase + kOptGroupWords * grp;
@@ -220,7 +248,7 @@ void sumsq_launch(const float* g, long long n, float* part, hipStream_t st) {
 }
 void adamw_launch(float* p, float* g, float* m, float* v, uint16_t* shadow, long long n, const float* hyper,
                   float eps, float wd, float clip, float gscale, int l2, int zero_g, const float* loss_src,
-                  float* loss_ring, int ring_n, const float* norm_part, hipStream_t st) {
+                  float* loss_ring, int ring_n, const float* norm_part, const float* guard, hipStream_t st) {
   const bool vec = n % 4 == 0 && ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) |
                                     reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v)) & 15) == 0 &&
                    (reinterpret_cast<uintptr_t>(shadow) & 7) == 0;
@@ -228,22 +256,22 @@ void adamw_launch(float* p, float* g, float* m, float* v, uint16_t* shadow, long
     hipLaunchKernelGGL(adamw4_kernel, grid_for(n / 4), dim3(256), 0, st, reinterpret_cast<float4*>(p),
                        reinterpret_cast<float4*>(g), reinterpret_cast<float4*>(m), reinterpret_cast<float4*>(v),
                        reinterpret_cast<uint2*>(shadow), n / 4, hyper, eps, wd, clip, gscale, l2, zero_g, loss_src,
-                       loss_ring, ring_n, norm_part);
+                       loss_ring, ring_n, norm_part, guard);
   else
     hipLaunchKernelGGL(adamw_kernel, grid_for(n), dim3(256), 0, st, p, g, m, v, shadow, n, hyper, eps, wd, clip, gscale,
-                       l2, zero_g, loss_src, loss_ring, ring_n, norm_part);
+                       l2, zero_g, loss_src, loss_ring, ring_n, norm_part, guard);
 }
 // p, g, m, v 16-byte aligned, shadow 8-byte aligned, hyper of 8 + 4 G floats (checked by the
 // binding); C chunks, T tensors, 1 ≤ G ≤ 8.  At most 2048 workgroups (8 per CU) walk the chunks.
 int adamw_grouped_launch(float* p, float* g, float* m, float* v, uint16_t* shadow, long long n, const float* hyper,
                          const long long* chunks, long long C, const int* tgroup, int T, int G, float clip, float gscale,
                          int l2, int zero_g, const float* loss_src, float* loss_ring, int ring_n,
-                         const float* norm_part, hipStream_t st) {
+                         const float* norm_part, const float* guard, hipStream_t st) {
   if (G < 1 || G > kOptMaxGroups) return -1;
   if (C <= 0 || T <= 0) return 0;
   const unsigned blocks = (unsigned)(C < 2048 ? C : 2048);
   hipLaunchKernelGGL(adamw_grouped_kernel, dim3(blocks), dim3(256), 0, st, p, g, m, v, shadow, n, hyper, chunks, C, tgroup,
-                     T, G, clip, gscale, l2, zero_g, loss_src, loss_ring, ring_n, norm_part);
+                     T, G, clip, gscale, l2, zero_g, loss_src, loss_ring, ring_n, norm_part, guard);
   return 0;
 }
 void fold_replicas_launch(float* grad, float* rep, long long n, int nrep, hipStream_t st) {

@@ -39,9 +39,9 @@ __device__ __forceinline__ OptChunk opt_chunk(const long long* __restrict__ chun
 }
 
 // ---- the step prologue ----------------------------------------------------------------------
-// the clip factor of a step from sumsq_kernel's partials, in a fixed order (every block of the grid
-// the same value): wave 0 sums the kSumsqBlocks partials, LDS broadcast
-__device__ __forceinline__ float opt_clip_scale(const float* __restrict__ part, float clip, float gscale) {
+// Σ g² of a step from sumsq_kernel's partials, in a fixed order (every block of every launch the same
+// value): wave 0 sums the kSumsqBlocks partials, LDS broadcast.  At least 64 threads per block.
+__device__ __forceinline__ float opt_sumsq_total(const float* __restrict__ part) {
   __shared__ float s_norm2;
   if (threadIdx.x < 64) {
     float t = 0.f;
@@ -51,34 +51,65 @@ __device__ __forceinline__ float opt_clip_scale(const float* __restrict__ part, 
     if (threadIdx.x == 0) s_norm2 = t;
   }
   __syncthreads();
-  const float norm = sqrtf(s_norm2) * gscale;
+  return s_norm2;
+}
+// the clip factor of a step from that sum
+__device__ __forceinline__ float opt_clip_scale(const float* __restrict__ part, float clip, float gscale) {
+  const float norm = sqrtf(opt_sumsq_total(part)) * gscale;
   const float f = clip / (norm + 1e-6f);
   return f < 1.f ? f : 1.f;
 }
 
 // hyper[0] = lr, [1] = step (already incremented), [3] = beta1, [4] = beta2, [5] = 1 − EMA decay,
-// [7] = loss-ring slot — read from device memory so schedulers can change them between replays of
+// [6] = "per-tensor statistics due this step" (non-zero: health.hip tensor_stats runs), [7] =
+// loss-ring slot — read from device memory so schedulers can change them between replays of
 // a captured step.
+//
+// guard (optional, null = off): the step guard's 8 fp32 words, owned by the optimizer and written by
+// health.hip step_guard_kernel between sumsq and the update:
+//   [0] skip flag of this step (1: Σ g² is not finite, the update must not happen)
+//   [1] steps skipped so far, this one included        [2] consecutive skipped steps, ending here
+//   [3] effective step = hyper[1] − steps skipped BEFORE this one: what the bias corrections take,
+//       so a skipped step does not advance them (GradScaler's meaning of a skip)
+//   [4] this step's gradient norm sqrt(Σ g²)·gscale (the mean gradient's, before clipping; inf / NaN
+//       as it comes)                                    [5] the last finite such norm
+//   [6] hyper[1] of the last skipped step (0: none)     [7] reserved
+// The flag is one word that every block of every launch of the step reads: the decision is uniform.
+constexpr int kGuardWords = 8;
+__device__ __forceinline__ bool opt_guard_skip(const float* __restrict__ guard) {
+  return guard != nullptr && guard[0] != 0.f;
+}
+__device__ __forceinline__ float opt_guard_step(const float* __restrict__ hyper, const float* __restrict__ guard) {
+  return guard != nullptr ? guard[3] : hyper[1];
+}
+// a float that is inf or NaN, by its exponent bits (no fast-math flag can fold this away)
+__device__ __forceinline__ bool opt_nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
+
 // loss_src (optional): the step's scalar loss, copied by thread 0 of block 0 into
 // loss_ring[hyper[7] % ring_n] (the step engine hands that slot back as the step's loss: no
-// separate copy launch per step).
+// separate copy launch per step) — on a skipped step too.
 // gs: what a gradient element is multiplied by.  g holds the all-reduced SUM over ranks (gscale =
 // 1 / world makes it the mean); with clip > 0 the threshold applies to the norm of the MEAN
 // gradient, as in single-process training, from sumsq_kernel's per-block partials (norm_part).
 // The bias corrections are each family's own (AdamW: 1 − powf, LAMB: lamb_bias_correction).
+// skip (a guard that flags this step): the caller clears the gradient it would have consumed (if it
+// clears gradients) and touches nothing else; step and gs are then meaningless.
 struct OptStep {
   float step, beta1, beta2, gs;
+  bool skip;
 };
 __device__ __forceinline__ OptStep opt_step(const float* __restrict__ hyper, float clip, float gscale,
                                             const float* __restrict__ loss_src, float* __restrict__ loss_ring,
-                                            int ring_n, const float* __restrict__ norm_part) {
+                                            int ring_n, const float* __restrict__ norm_part,
+                                            const float* __restrict__ guard) {
   OptStep s;
-  s.step = hyper[1];
+  s.step = opt_guard_step(hyper, guard);
+  s.skip = opt_guard_skip(guard);
   s.beta1 = hyper[3];
   s.beta2 = hyper[4];
   if (loss_src != nullptr && blockIdx.x == 0 && threadIdx.x == 0) loss_ring[(int)hyper[7] % ring_n] = *loss_src;
   s.gs = gscale;
-  if (clip > 0.f) s.gs *= opt_clip_scale(norm_part, clip, gscale);
+  if (clip > 0.f && !s.skip) s.gs *= opt_clip_scale(norm_part, clip, gscale);  // uniform over the launch
   return s;
 }
 

@@ -896,20 +896,51 @@ def sumsq(g, part):
     part[0] = (g.float() ** 2).sum()
 
 
-def _opt_prologue(hyper, clip, gscale, norm_part, loss_src, loss_ring):
+GUARD_WORDS = 8  # csrc/optim_common.h kGuardWords
+
+
+def step_guard(part, hyper, guard, gscale):
+    """csrc/health.hip step_guard_kernel: judge the gradient's Σ g² (``sumsq``'s partials, summed in
+    fp32) and rewrite the optimizer's 8 guard words (fp32, layout in csrc/optim_common.h):
+    ``[0]`` skip flag of this step (Σ g² inf or NaN — a finite gradient whose Σ g² overflows fp32
+    included), ``[1]`` steps skipped so far, ``[2]`` consecutive skipped steps, ``[3]`` effective step
+    ``hyper[1]`` − steps skipped before this one, ``[4]`` this step's norm ``sqrt(Σ)·gscale``,
+    ``[5]`` the last finite norm, ``[6]`` ``hyper[1]`` of the last skipped step, ``[7]`` reserved."""
+    total = part.to(torch.float32).sum()
+    skip = not bool(torch.isfinite(total))
+    norm = total.sqrt() * torch.tensor(gscale, dtype=torch.float32)
+    step, old = hyper[1].to(torch.float32), guard.clone()
+    guard[0] = 1.0 if skip else 0.0
+    guard[1] = old[1] + 1 if skip else old[1]
+    guard[2] = old[2] + 1 if skip else 0.0
+    guard[3] = step - old[1]
+    guard[4] = norm
+    guard[5] = old[5] if skip else norm
+    guard[6] = step if skip else old[6]
+    guard[7] = 0.0
+
+
+def _opt_prologue(hyper, clip, gscale, norm_part, loss_src, loss_ring, guard=None):
     """What every flat-space update starts with (csrc/optim_common.h opt_step): the step's loss into
-    the engine's ring slot ``hyper[7]``, then → (step, beta1, beta2, gs) with ``gs`` the factor of a
-    gradient element: ``gscale`` times the clip factor ``min(1, clip / (‖g‖·gscale + 1e-6))``."""
+    the engine's ring slot ``hyper[7]``, then → (step, beta1, beta2, gs, skip) with ``gs`` the factor
+    of a gradient element: ``gscale`` times the clip factor ``min(1, clip / (‖g‖·gscale + 1e-6))``.
+    ``guard`` (the words :func:`step_guard` wrote): the step is its effective step ``guard[3]``, and
+    ``skip`` tells the caller to clear the gradient it would have consumed and touch nothing else."""
     step, b1, b2 = float(hyper[1]), float(hyper[3]), float(hyper[4])
+    skip = False
+    if guard is not None:
+        step, skip = float(guard[3]), float(guard[0]) != 0.0
     if loss_src is not None:
         loss_ring.view(-1)[int(float(hyper[7])) % loss_ring.numel()] = loss_src.reshape(())
     gs = gscale
+    if skip:
+        return step, b1, b2, gs, True
     if clip > 0:
         norm = math.sqrt(float(norm_part.sum())) * gscale  # norm of the mean (all-reduced sum × 1/world)
         f = clip / (norm + 1e-6)
         if f < 1:
             gs *= f
-    return step, b1, b2, gs
+    return step, b1, b2, gs, False
 
 
 def _adamw_range(p, g, m, v, shadow, lr, wd, eps, b1, b2, bc1, bc2, gs, l2, zero_grad):
@@ -930,8 +961,12 @@ def _adamw_range(p, g, m, v, shadow, lr, wd, eps, b1, b2, bc1, bc2, gs, l2, zero
 
 
 def adamw(p, g, m, v, shadow, hyper, eps, wd, clip, gscale, l2=False, zero_grad=False, loss_src=None, loss_ring=None,
-          norm_part=None):
-    step, b1, b2, gs = _opt_prologue(hyper, clip, gscale, norm_part, loss_src, loss_ring)
+          norm_part=None, guard=None):
+    step, b1, b2, gs, skip = _opt_prologue(hyper, clip, gscale, norm_part, loss_src, loss_ring, guard)
+    if skip:
+        if zero_grad:
+            g.zero_()
+        return
     _adamw_range(p, g, m, v, shadow, float(hyper[0]), wd, eps, b1, b2, 1 - b1 ** step, 1 - b2 ** step, gs, l2, zero_grad)
 
 
@@ -948,13 +983,19 @@ def _tensor_ranges(chunk_tab):
 
 
 def adamw_grouped(p, g, m, v, shadow, hyper, chunk_tab, tensor_group, groups, clip, gscale, l2=False, zero_grad=False,
-                  loss_src=None, loss_ring=None, norm_part=None):
+                  loss_src=None, loss_ring=None, norm_part=None, guard=None):
     """AdamW with per-group lr / weight decay / eps, tensor by tensor (csrc/optim.hip
     adamw_grouped_kernel): tensor ``t`` takes ``hyper[8 + 4j : 8 + 4j + 3]`` of its group
     ``j = tensor_group[t]``; step, betas, the clip factor (the norm of all groups together),
     ``gscale``, ``l2`` and ``zero_grad`` are those of :func:`adamw`.  Padding between tensors belongs
-    to no chunk and is left alone."""
-    step, b1, b2, gs = _opt_prologue(hyper, clip, gscale, norm_part, loss_src, loss_ring)
+    to no chunk and is left alone.  ``guard``: as for :func:`adamw` (a skipped step clears the tensors'
+    gradients with ``zero_grad`` and nothing else)."""
+    step, b1, b2, gs, skip = _opt_prologue(hyper, clip, gscale, norm_part, loss_src, loss_ring, guard)
+    if skip:
+        if zero_grad:
+            for _, lo, hi in _tensor_ranges(chunk_tab):
+                g[lo:hi].zero_()
+        return
     bc1, bc2 = 1 - b1 ** step, 1 - b2 ** step
     hv, tg = hyper.tolist(), tensor_group.tolist()
     for t, lo, hi in _tensor_ranges(chunk_tab):
@@ -967,16 +1008,22 @@ def adamw_grouped(p, g, m, v, shadow, hyper, chunk_tab, tensor_group, groups, cl
 
 
 def lamb(p, g, m, v, shadow, hyper, chunk_tab, tensor_tab, tensor_opt, partials, trust, eps, clip, gscale,
-         zero_grad=False, loss_src=None, loss_ring=None, norm_part=None, tensor_group=None):
+         zero_grad=False, loss_src=None, loss_ring=None, norm_part=None, tensor_group=None, guard=None):
     """LAMB over the flat buffers, tensor by tensor (csrc/lamb.hip; the tables of
     ``ops.optim.lamb_tables``): u = m̂ / (sqrt(v̂) + eps) + wd·w, trust = ‖w‖ / ‖u‖ for adapted
     tensors with non-zero norms (else 1), w ← w − lr·trust·u.  Padding between tensors belongs to
     no chunk and is left alone.  ``partials`` is the kernels' scratch: unused here.
     ``tensor_group`` (T,): tensor ``t`` takes its group's lr ``hyper[8 + 4·tensor_group[t]]``
-    (None: every tensor group 0's, ``hyper[0]``)."""
+    (None: every tensor group 0's, ``hyper[0]``).  ``guard``: as for :func:`adamw`; a skipped step
+    also keeps ``trust``."""
     lr = float(hyper[0])
     lrs = None if tensor_group is None else [float(hyper[8 + 4 * j]) for j in tensor_group.tolist()]
-    step, b1, b2, gs = _opt_prologue(hyper, clip, gscale, norm_part, loss_src, loss_ring)
+    step, b1, b2, gs, skip = _opt_prologue(hyper, clip, gscale, norm_part, loss_src, loss_ring, guard)
+    if skip:
+        if zero_grad:
+            for _, lo, hi in _tensor_ranges(chunk_tab):
+                g[lo:hi].zero_()
+        return
     bc1, bc2s = 1 - b1 ** step, math.sqrt(1 - b2 ** step)
     chunks, tensors, opts = chunk_tab.tolist(), tensor_tab.tolist(), tensor_opt.tolist()
     for t, ((first, cnt), (wd, adapt)) in enumerate(zip(tensors, opts)):
@@ -999,9 +1046,36 @@ def lamb(p, g, m, v, shadow, hyper, chunk_tab, tensor_tab, tensor_opt, partials,
             shadow[lo:hi].copy_(w.to(shadow.dtype))
 
 
+def tensor_stats(g, w, hyper, chunk_tab, tensor_tab, part, stats, gscale, guard=None, skip_stats=None):
+    """csrc/health.hip tensor_stats: per tensor of the chunk table, ``stats[t]`` = (‖g‖·gscale, ‖w‖,
+    max|g|·gscale, non-finite gradient elements) in fp32, from fp64 sums.  The maximum ignores NaN
+    elements (the count tells of them); padding belongs to no chunk and is never read.  Nothing is
+    written unless ``hyper[6]`` (statistics due) is non-zero; with a ``guard`` that flags this step the
+    rows (also) go to ``skip_stats``.  ``part`` is the kernels' scratch: unused here."""
+    due = float(hyper[6]) != 0.0
+    skip = guard is not None and float(guard[0]) != 0.0
+    if not (due or skip):
+        return
+    chunks = chunk_tab.tolist()
+    rows = []
+    for first, cnt in tensor_tab.tolist():
+        lo = chunks[first][0]
+        hi = lo + sum(c[1] for c in chunks[first:first + cnt])
+        gt, wt = g[lo:hi].double(), w[lo:hi].double()
+        mx = torch.where(torch.isnan(gt), torch.zeros_like(gt), gt.abs()).max() if hi > lo else gt.new_zeros(())
+        rows.append(torch.stack([gt.pow(2).sum().sqrt().float() * gscale, wt.pow(2).sum().sqrt().float(),
+                                 mx.float() * gscale, (~torch.isfinite(gt)).sum().float()]))
+    out = torch.stack(rows).to(stats.dtype)
+    if due:
+        stats.view(-1, 4)[:len(rows)].copy_(out)
+    if skip and skip_stats is not None:
+        skip_stats.view(-1, 4)[:len(rows)].copy_(out)
+
+
 def ema_update(ema, w, hyper):
     """csrc/ema.hip ema_update_kernel: ema ← ema + omd·(w − ema) with omd = hyper[5] (1 − decay of
-    this step), as three separately rounded fp32 operations; omd == 0 leaves ema untouched and
+    this step), as three separately rounded fp32 operations; not gated by the step guard: on a skipped
+    step the weights did not move and are averaged again, as an eager recipe behind ``GradScaler`` does; omd == 0 leaves ema untouched and
     omd == 1 (decay = 0) copies w, which ema + (w − ema) misses by a rounding where the two are
     more than a factor of two apart."""
     if ema.numel() % 4:

@@ -29,6 +29,11 @@ the chunk table of the flat buffer (csrc/optim.hip); one group runs the single-g
 fused update takes per-tensor trust ratios and per-tensor weight decay from chunk tables
 (``lamb_tables``, csrc/lamb.hip; what the updates share on the device is csrc/optim_common.h).
 
+``skip_nonfinite`` (every fused optimizer) puts a step guard in front of the update: one more small
+launch judges the gradient's Σ g² on the device and an update whose gradient is not finite does not
+happen — inside a replayed graph, with no host in the loop (csrc/health.hip).  ``tensor_stats`` adds
+per-tensor gradient / weight norms on request (``request_stats``), the trainer's ``track_grad_norm``.
+
 ``WeightEMA`` keeps an exponential moving average of the weights as one more flat fp32 buffer,
 updated by one launch behind the fused update and swapped in for evaluation (csrc/ema.hip).
 """
@@ -172,10 +177,28 @@ class _HostRing:
 
 
 class FusedAdamW(torch.optim.Optimizer):
-    """AdamW over a :class:`FlatParameterSpace` in one kernel (HIP) or its emulation (CPU)."""
+    """AdamW over a :class:`FlatParameterSpace` in one kernel (HIP) or its emulation (CPU).
+
+    ``skip_nonfinite``: a step whose gradient is not finite (Σ g² inf or NaN, a finite gradient whose
+    Σ g² overflows fp32 included) is skipped on the device: ``sumsq`` → ``step_guard`` → the update with
+    the guard's words.  A skipped step leaves weights, moments and shadow as they are, still clears the
+    gradient and still delivers the loss, and does not advance the bias corrections (they take the
+    *effective* step: attempted − skipped, ``GradScaler``'s meaning of a skip), so a run with one
+    poisoned step and a constant learning rate ends bit for bit where the run without that step ends.
+    The host's schedules (``lr``, the EMA decay) are functions of the attempted step and keep advancing
+    on skipped steps; an attached :class:`WeightEMA` is not gated either: the weights did not move, so
+    it averages them once more, as an eager recipe behind ``GradScaler`` does.  :meth:`health` reads the
+    counters.  With data parallelism the guard judges the all-reduced gradient, so every rank decides
+    alike.  The guard needs the global norm: no per-bucket or range updates.
+
+    ``tensor_stats``: per-tensor ‖g‖, ‖w‖, max|g| and non-finite counts (:meth:`request_stats`,
+    :meth:`tensor_stats`; with ``skip_nonfinite`` also of the last skipped step,
+    :meth:`skipped_tensor_stats`).  With both options off the optimizer has no extra launch, buffer or
+    hyper word."""
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
-                 amsgrad: bool = False, max_grad_norm: float = 0.0, flat: Optional[FlatParameterSpace] = None):
+                 amsgrad: bool = False, max_grad_norm: float = 0.0, flat: Optional[FlatParameterSpace] = None,
+                 skip_nonfinite: bool = False, tensor_stats: bool = False):
         if amsgrad:
             raise NotImplementedError("amsgrad is not supported by the fused optimizer")
         params = list(params)
@@ -212,7 +235,14 @@ class FusedAdamW(torch.optim.Optimizer):
         self.max_grad_norm = float(max_grad_norm)
         # the gradient's sum of squares as fixed-order per-block partials (sumsq → adamw norm_part):
         # no atomics, so the clip factor is bitwise reproducible in every mode
-        self.norm_part = torch.zeros(512, dtype=torch.float32, device=dev) if self.max_grad_norm > 0 else None
+        self.skip_nonfinite, self.track_stats = bool(skip_nonfinite), bool(tensor_stats)
+        self.norm_part = (torch.zeros(512, dtype=torch.float32, device=dev)
+                          if self.max_grad_norm > 0 or self.skip_nonfinite else None)
+        # the step guard's 8 words (csrc/optim_common.h), written by step_guard on the device
+        self.guard = torch.zeros(8, dtype=torch.float32, device=dev) if self.skip_nonfinite else None
+        self._stats_due = False
+        if self.track_stats:
+            self._build_stats_buffers()
         self.l2 = False  # decoupled decay (AdamW); FusedAdam sets the coupled L2 form
         self._step = 0
         self._ring = _HostRing(8, self.hyper.numel(), dev) if dev.type == "cuda" else None
@@ -227,6 +257,53 @@ class FusedAdamW(torch.optim.Optimizer):
         self.loss_slot = 0
         self.ema = None  # attach_ema: a WeightEMA over self.flat, updated right behind every update
 
+    def _build_stats_buffers(self):
+        """The tables and buffers of ``tensor_stats``: the chunk table of the flat buffer (the one a
+        grouped or LAMB update already has, else built here), tensor → (first chunk, chunks), the
+        per-chunk scratch and the (T, 4) results (a second one for skipped steps with a guard)."""
+        f = self.flat
+        chunks, tensors = _cut_chunks(f.offsets, [p.numel() for p in f.params])
+        if getattr(self, "chunk_tab", None) is None:
+            self.chunk_tab = torch.tensor(chunks, dtype=torch.int64, device=f.device).reshape(-1, 3)
+        self.stats_tensor_tab = torch.tensor(tensors, dtype=torch.int32, device=f.device).reshape(-1, 2)
+        self.stats_part = torch.zeros(4 * len(chunks), dtype=torch.float32, device=f.device)
+        self.stats = torch.zeros(len(tensors), 4, dtype=torch.float32, device=f.device)
+        self.skip_stats = torch.zeros_like(self.stats) if self.skip_nonfinite else None
+
+    # -- health -------------------------------------------------------------------------
+    def health(self) -> dict:
+        """The step guard's counters, one host read (a sync): ``skipped`` steps so far, ``consecutive``
+        skipped steps ending at the last one, ``last_norm`` (the last step's gradient norm, the mean
+        gradient's before clipping, non-finite as it came), ``last_finite_norm`` and
+        ``last_skipped_step`` (1-based attempted step, 0: none)."""
+        if self.guard is None:
+            raise RuntimeError(f"{type(self).__name__}.health() needs skip_nonfinite=True")
+        w = self.guard.tolist()
+        return {"skipped": int(w[1]), "consecutive": int(w[2]), "last_norm": w[4], "last_finite_norm": w[5],
+                "last_skipped_step": int(w[6])}
+
+    def request_stats(self):
+        """Make the next staged step a statistics step (``hyper[6]``): its update is preceded by the
+        per-tensor statistics launches, read back with :meth:`tensor_stats`."""
+        if not self.track_stats:
+            raise RuntimeError(f"{type(self).__name__}.request_stats() needs tensor_stats=True")
+        self._stats_due = True
+
+    def tensor_stats(self) -> torch.Tensor:
+        """(T, 4) fp32 per tensor of ``flat.params``, of the last statistics step: ‖g‖ (of the mean
+        gradient, before clipping), ‖w‖ (before the update), max|g| (NaN elements ignored) and the
+        number of non-finite gradient elements."""
+        if not self.track_stats:
+            raise RuntimeError(f"{type(self).__name__}.tensor_stats() needs tensor_stats=True")
+        return self.stats
+
+    def skipped_tensor_stats(self) -> torch.Tensor:
+        """The same rows of the most recent skipped step (kept until the next skipped step)."""
+        if not self.track_stats or self.skip_stats is None:
+            raise RuntimeError(f"{type(self).__name__}.skipped_tensor_stats() needs tensor_stats=True and "
+                               f"skip_nonfinite=True")
+        return self.skip_stats
+
     def attach_ema(self, ema: Optional["WeightEMA"]):
         """Average the weights after every update: ``hyper[5]`` carries the step's 1 − decay and one
         more launch (``ema_update``) follows the update kernel, inside a captured step too."""
@@ -239,7 +316,9 @@ class FusedAdamW(torch.optim.Optimizer):
     # -- the update ---------------------------------------------------------------------
     def hyper_values(self):
         """lr / step / betas of the NEXT update (and the step engine's loss-ring slot; with an
-        attached :class:`WeightEMA` its 1 − decay of that step, else 0), in ``self.hyper``'s layout."""
+        attached :class:`WeightEMA` its 1 − decay of that step, else 0; word 6 is 1 on a statistics
+        step, :meth:`request_stats`), in ``self.hyper``'s layout.  Taking the values consumes a
+        statistics request: they are staged exactly once per step."""
         g = self.param_groups[0]
         b1, b2 = g["betas"]
         # every update, eager or replayed, stages these first: the place to refuse one that would
@@ -247,7 +326,8 @@ class FusedAdamW(torch.optim.Optimizer):
         if self.ema is not None and self.ema.swapped:
             raise RuntimeError("optimizer step while the averaged weights are swapped in (WeightEMA.swap)")
         omd = 0.0 if self.ema is None else self.ema.one_minus_decay(self._step + 1)
-        vals = [float(g["lr"]), float(self._step + 1), 0.0, float(b1), float(b2), omd, 0.0, float(self.loss_slot)]
+        due, self._stats_due = (1.0 if self._stats_due else 0.0), False
+        vals = [float(g["lr"]), float(self._step + 1), 0.0, float(b1), float(b2), omd, due, float(self.loss_slot)]
         if len(self.param_groups) > 1:  # the group words: every group's scheduled lr reaches a replayed step
             for g in self.param_groups:
                 vals += [float(g["lr"]), float(g["weight_decay"]), float(g["eps"]), 0.0]
@@ -267,7 +347,7 @@ class FusedAdamW(torch.optim.Optimizer):
         a weight EMA (the side-stream updates would finish after its launch); a range knows no
         tensor boundaries, so several parameter groups take the whole-buffer update too."""
         return (self.max_grad_norm <= 0 and self.flat.grad_rep is None and self.ema is None
-                and len(self.param_groups) == 1)
+                and len(self.param_groups) == 1 and not self.skip_nonfinite and not self.track_stats)
 
     def range_update(self, lo: int, hi: int):
         """Fused AdamW over flat elements [lo, hi) only (the same per-element arithmetic as the
@@ -276,6 +356,8 @@ class FusedAdamW(torch.optim.Optimizer):
         for this step."""
         if len(self.param_groups) > 1:
             raise NotImplementedError("range updates take one parameter group (a range knows no tensor boundaries)")
+        if self.skip_nonfinite:
+            raise NotImplementedError("range updates know no global gradient norm: none with skip_nonfinite")
         g = self.param_groups[0]
         f = self.flat
         _kernels(f.device).adamw(f.data[lo:hi], f.grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi],
@@ -283,8 +365,8 @@ class FusedAdamW(torch.optim.Optimizer):
                                  0.0, self.grad_scale, l2=self.l2, zero_grad=True)
 
     def device_update(self, zero_grad: bool = False):
-        """The capturable part: fold, (grad-norm), the fused update over the flat buffers
-        (:meth:`_launch_update`), the EMA launch.
+        """The capturable part: fold, (grad-norm, step guard, per-tensor statistics), the fused update
+        over the flat buffers (:meth:`_launch_update`), the EMA launch (not gated by the guard).
         ``zero_grad``: the kernel clears the gradient as it consumes it (flat buffers without
         replicas only; the step engine's captured step then skips its leading zero fill).
         In bucket mode the reducer has already updated every bucket: nothing to do."""
@@ -293,11 +375,18 @@ class FusedAdamW(torch.optim.Optimizer):
         f = self.flat
         K = _kernels(f.device)
         f.fold()
-        if self.max_grad_norm > 0:
+        if self.norm_part is not None:
             K.sumsq(f.grad, self.norm_part)
+        more = {}
+        if self.guard is not None:  # a trailing keyword of the update only when on
+            K.step_guard(self.norm_part, self.hyper, self.guard, self.grad_scale)
+            more["guard"] = self.guard
+        if self.track_stats:  # while g and w are still this step's; returns at once unless due / skipped
+            K.tensor_stats(f.grad, f.data, self.hyper, self.chunk_tab, self.stats_tensor_tab, self.stats_part,
+                           self.stats, self.grad_scale, guard=self.guard, skip_stats=self.skip_stats)
         lo = self.loss_out
         self._launch_update(K, zero_grad=zero_grad and f.grad_rep is None, loss_src=None if lo is None else lo[0],
-                            loss_ring=None if lo is None else lo[1], norm_part=self.norm_part)
+                            loss_ring=None if lo is None else lo[1], norm_part=self.norm_part, **more)
         if self.ema is not None:
             K.ema_update(self.ema.avg, f.data, self.hyper)
 
@@ -341,8 +430,10 @@ class FusedAdamW(torch.optim.Optimizer):
         sd = super().state_dict()
         state = {}
         ea, es = self.flat.views(self.exp_avg), self.flat.views(self.exp_avg_sq)
+        # with a step guard: the effective step, the one the bias corrections have seen
+        step = self._step - (int(self.guard[1]) if self.guard is not None else 0)
         for k, i in self._state_index().items():
-            state[k] = {"step": torch.tensor(float(self._step)), "exp_avg": ea[i].clone(), "exp_avg_sq": es[i].clone()}
+            state[k] = {"step": torch.tensor(float(step)), "exp_avg": ea[i].clone(), "exp_avg_sq": es[i].clone()}
         sd["state"] = state
         return sd
 
@@ -363,6 +454,8 @@ class FusedAdamW(torch.optim.Optimizer):
                 es[i].copy_(st["exp_avg_sq"])
             step = int(float(st.get("step", 0)))
         self._step = step
+        if self.guard is not None:  # the loaded step is an effective one: the counters start over
+            self.guard.zero_()
 
 
 class FusedAdam(FusedAdamW):
@@ -374,9 +467,10 @@ class FusedAdam(FusedAdamW):
     gradient (torch skips ``grad is None``) out of ``params``."""
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
-                 amsgrad: bool = False, max_grad_norm: float = 0.0, flat: Optional[FlatParameterSpace] = None):
+                 amsgrad: bool = False, max_grad_norm: float = 0.0, flat: Optional[FlatParameterSpace] = None,
+                 skip_nonfinite: bool = False, tensor_stats: bool = False):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad,
-                         max_grad_norm=max_grad_norm, flat=flat)
+                         max_grad_norm=max_grad_norm, flat=flat, skip_nonfinite=skip_nonfinite, tensor_stats=tensor_stats)
         self.l2 = True
 
 
@@ -527,9 +621,10 @@ class FusedLamb(FusedAdamW):
     trust ratios need whole tensors, so there are no per-bucket or range updates."""
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-6, weight_decay: float = 0.01,
-                 exclude_1d: bool = True, max_grad_norm: float = 0.0, flat: Optional[FlatParameterSpace] = None):
+                 exclude_1d: bool = True, max_grad_norm: float = 0.0, flat: Optional[FlatParameterSpace] = None,
+                 skip_nonfinite: bool = False, tensor_stats: bool = False):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
-                         flat=flat)
+                         flat=flat, skip_nonfinite=skip_nonfinite, tensor_stats=tensor_stats)
         for g in self.param_groups:  # a group option, as in Lamb
             g.setdefault("exclude_1d", bool(exclude_1d))
             # the LAMB kernels take one eps: refuse what plain Lamb would honour per group

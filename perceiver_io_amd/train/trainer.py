@@ -6,7 +6,11 @@ setup → configure_optimizers → parameter broadcast → sanity validation →
 Flags mirror ``scripts/trainer.yaml`` (max_steps / max_epochs, limit_*_batches,
 val_check_interval, check_val_every_n_epoch, log_every_n_steps, num_sanity_val_steps,
 accumulate_grad_batches, gradient_clip_val, precision, resume_from_checkpoint,
-fast_dev_run, overfit_batches, terminate_on_nan, detect_anomaly, deterministic, profiler).
+fast_dev_run, overfit_batches, terminate_on_nan, detect_anomaly, deterministic, profiler,
+track_grad_norm), plus ``skip_nonfinite_steps`` / ``max_skipped_steps`` (no counterpart in the
+reference): an update whose gradient is not finite is skipped — on the device inside the replayed
+step (``ops.optim`` ``skip_nonfinite``), with plain torch ops on the eager path — instead of
+poisoning weights and moments until ``terminate_on_nan`` notices at the next log interval.
 
 MI355X specifics:
   * ``precision`` ``bf16`` (default in this framework's trainer.yaml) runs the fused HIP
@@ -111,7 +115,8 @@ class Trainer:
                  deterministic: bool = False, detect_anomaly: bool = False, terminate_on_nan: Optional[bool] = None,
                  replace_sampler_ddp: bool = True, graph_capture: Optional[bool] = None, seed: Optional[int] = None,
                  allreduce_dtype: Optional[str] = None, ema_decay: Optional[float] = None, ema_warmup: bool = True,
-                 ema_update_every: int = 1, ema_eval: bool = True, **ignored: Any):
+                 ema_update_every: int = 1, ema_eval: bool = True, skip_nonfinite_steps: bool = False,
+                 max_skipped_steps: int = 25, track_grad_norm: Any = -1, **ignored: Any):
         for k, v in ignored.items():
             if v not in (None, False, 0, 0.0, "", [], {}) and k not in _KNOWN_NOOP:
                 warnings.warn(f"Trainer flag {k}={v!r} has no effect in this framework")
@@ -162,6 +167,15 @@ class Trainer:
         self.ema_update_every = int(ema_update_every or 1)
         self.ema_eval = bool(ema_eval)
         self.ema = None  # built by fit
+        # step guard: skip updates with a non-finite gradient; more than max_skipped_steps of them in a
+        # row (a policy value, not a measurement) raises at the log interval
+        self.skip_nonfinite_steps = bool(skip_nonfinite_steps)
+        self.max_skipped_steps = int(25 if max_skipped_steps is None else max_skipped_steps)
+        self.track_grad_norm = _norm_type(track_grad_norm)  # None (off), 2.0 or inf
+        self._skips_reported = 0
+        self._eager_health = None  # the eager path's counters (the fused optimizers keep theirs on the device)
+        self._eager_stats = None
+        self.skip_report = ""  # the last report of a skipped step
         if fast_dev_run:
             n = 1 if fast_dev_run is True else int(fast_dev_run)
             self.limit_train_batches = self.limit_val_batches = self.limit_test_batches = n
@@ -297,13 +311,14 @@ class Trainer:
             if kind == "Lamb":
                 new = FusedLamb(groups, lr=g["lr"], betas=g["betas"], eps=g["eps"],
                                 weight_decay=g.get("weight_decay", 0.0), exclude_1d=g.get("exclude_1d", True),
-                                max_grad_norm=self.gradient_clip_val or getattr(opt, "max_grad_norm", 0.0), flat=flat)
+                                max_grad_norm=self.gradient_clip_val or getattr(opt, "max_grad_norm", 0.0), flat=flat,
+                                **self._health_options())
             else:
                 if kind == "Adam" and any(g.get("weight_decay", 0.0) for g in groups):
                     warnings.warn("Adam with L2 weight decay is executed as decoupled AdamW by the fused optimizer")
                 new = FusedAdamW(groups, lr=g["lr"], betas=g["betas"], eps=g["eps"],
                                  weight_decay=g.get("weight_decay", 0.0), max_grad_norm=self.gradient_clip_val,
-                                 flat=flat)
+                                 flat=flat, **self._health_options())
             if sched is not None:
                 init = getattr(model.hparams, "get", lambda *_: None)("scheduler_init")
                 if init is not None:
@@ -316,6 +331,82 @@ class Trainer:
                     sched = None
             opt = new
         return opt, sched
+
+    # ---- training health: step guard and gradient norms ---------------------------------------
+    def _health_options(self) -> dict:
+        """The fused optimizers' options for this trainer's flags (none when both are off)."""
+        opts = {}
+        if self.skip_nonfinite_steps:
+            opts["skip_nonfinite"] = True
+        if self.track_grad_norm is not None:
+            opts["tensor_stats"] = True
+        return opts
+
+    @property
+    def _eager_health_on(self) -> bool:
+        return not self._fused_opt and (self.skip_nonfinite_steps or self.track_grad_norm is not None)
+
+    @property
+    def _fused_opt(self) -> bool:
+        from ..ops.optim import FusedAdamW
+
+        return bool(self.optimizers) and isinstance(self.optimizers[0], FusedAdamW)
+
+    def _log_step_next(self) -> bool:
+        """Will the step about to run be logged?"""
+        return (self.global_step + 1) % self.log_every_n_steps == 0 or self.fast_dev_run
+
+    def _health(self) -> dict:
+        if self._fused_opt:
+            return self.optimizers[0].health()
+        return dict(self._eager_health or {"skipped": 0, "consecutive": 0, "last_norm": 0.0, "last_finite_norm": 0.0,
+                                           "last_skipped_step": 0})
+
+    def _stats_names(self):
+        """(parameter names, (T, 4) statistics of the logged step, those of the last skipped step or None)."""
+        if self._fused_opt:
+            opt = self.optimizers[0]
+            if not opt.track_stats:
+                return [], None, None
+            names = parameter_names(self.model, opt.flat.params)
+            return names, opt.tensor_stats().cpu(), None if opt.skip_stats is None else opt.skipped_tensor_stats().cpu()
+        if self._eager_stats is None:
+            return [], None, None
+        return self._eager_stats
+
+    def _health_logs(self, vals: Dict[str, float]):
+        """At a log interval (the host already syncs for the loss there): ``skipped_steps``, the
+        report of new skips, the limit on consecutive ones, and the ``track_grad_norm`` keys."""
+        names, stats, skipped = self._stats_names() if (self.track_grad_norm is not None or self.skip_nonfinite_steps) \
+            else ([], None, None)
+        if self.skip_nonfinite_steps:
+            h = self._health()
+            vals["skipped_steps"] = float(h["skipped"])
+            if h["skipped"] > self._skips_reported or h["consecutive"] > self.max_skipped_steps:
+                bad = [] if skipped is None else [n for n, row in zip(names, skipped.tolist()) if row[3] > 0]
+                self.skip_report = (
+                    f"step {h['last_skipped_step']}: the gradient was not finite and the update was skipped "
+                    f"({h['skipped']} skipped so far, {h['consecutive']} in a row; last gradient norm {h['last_norm']:.4g}, "
+                    f"last finite one {h['last_finite_norm']:.4g})"
+                    + (f"; tensors with non-finite gradients: {', '.join(bad[:8])}"
+                       + (f" and {len(bad) - 8} more" if len(bad) > 8 else "") if bad else ""))
+                self._skips_reported = h["skipped"]
+                if h["consecutive"] > self.max_skipped_steps:
+                    raise RuntimeError(f"more than max_skipped_steps={self.max_skipped_steps} consecutive skipped "
+                                       f"steps at step {self.global_step}: {self.skip_report}")
+                if self.is_global_zero:
+                    print(self.skip_report, file=sys.stderr, flush=True)
+        if self.track_grad_norm is not None and stats is not None:
+            rows = stats.tolist()
+            if self.track_grad_norm == 2.0:
+                # the total: the guard's norm of this very step when there is one, else from the per-tensor norms
+                total = self._health()["last_norm"] if self.skip_nonfinite_steps and self._fused_opt \
+                    else math.sqrt(sum(r[0] * r[0] for r in rows))
+                vals["grad_2.0_norm_total"] = total
+                vals.update({f"grad_2.0_norm/{n}": r[0] for n, r in zip(names, rows)})
+            else:
+                vals["grad_inf_norm_total"] = max((r[2] for r in rows), default=0.0)
+                vals.update({f"grad_inf_norm/{n}": r[2] for n, r in zip(names, rows)})
 
     def _attach(self, model, datamodule):
         self.model = model
@@ -446,6 +537,11 @@ class Trainer:
     _cur_bs = 1
     ema = None  # the WeightEMA of the current fit (ema_decay set), else None
     ema_eval = True
+    skip_nonfinite_steps = False  # the step guard and the gradient norms: off
+    track_grad_norm = None
+    max_skipped_steps = 25
+    _eager_health = _eager_stats = None
+    _skips_reported = 0
 
     def _restore_step_logs(self, logs):
         self._step_logs = dict(logs)
@@ -489,8 +585,10 @@ class Trainer:
                 acc_buf.append(batch)
                 if len(acc_buf) < self.accumulate:
                     continue
+                if self.track_grad_norm is not None and self._fused_opt and self._log_step_next():
+                    self.optimizers[0].request_stats()  # staged with this step's hyper-parameters
                 with self.timer("training_step_and_update"):
-                    if not self.fused and self.gradient_clip_val:
+                    if (not self.fused and self.gradient_clip_val) or self._eager_health_on:
                         loss = self._eager_clip_step(acc_buf)
                     else:
                         loss = self._engine.step(acc_buf if self.accumulate > 1 else acc_buf[0], ring_view=True)
@@ -508,6 +606,8 @@ class Trainer:
                     sps = (self.global_step - steps_last) / max(now - t_last, 1e-9)
                     t_last, steps_last = now, self.global_step
                     vals["steps_per_sec"] = sps
+                    if self.skip_nonfinite_steps or self.track_grad_norm is not None:
+                        self._health_logs(vals)
                     self.callback_metrics.update(vals)
                     self.log_scalars(vals)
                     ops.mlm_head.check_overflow()  # fixed-capacity MLM rows: fail loudly, never truncate
@@ -515,7 +615,7 @@ class Trainer:
                     if self.terminate_on_nan and not all(math.isfinite(v) for v in vals.values()):
                         raise ValueError(f"non-finite metric at step {self.global_step}: {vals}")
                     if self.enable_progress_bar and self.is_global_zero:
-                        pb = " ".join(f"{k}={v:.4g}" for k, v in vals.items())
+                        pb = " ".join(f"{k}={v:.4g}" for k, v in vals.items() if "_norm/" not in k)  # per-tensor: logger only
                         print(f"epoch {self.current_epoch} step {self.global_step} {pb}", file=sys.stderr, flush=True)
                 if 0 < self.max_steps <= self.global_step:
                     self.should_stop = True
@@ -544,8 +644,11 @@ class Trainer:
                 for p in self.model.parameters():
                     if p.grad is not None:
                         p.grad.mul_(red.grad_scale())
-        torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.gradient_clip_val)
-        opt.step()
+        skip = self._eager_health_on and self._eager_judge()
+        if self.gradient_clip_val and not skip:
+            torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.gradient_clip_val)
+        if not skip:  # a skipped step: no update (the optimizer's own step count is the effective one),
+            opt.step()  # while the EMA and the schedule below keep advancing, as on the fused path
         if self.ema is not None:
             self.ema.update(self.global_step + 1)  # the step just taken, 1-based
         for s in self.lr_schedulers:
@@ -555,6 +658,37 @@ class Trainer:
         else:
             opt.zero_grad()
         return loss.detach()
+
+    @torch.no_grad()
+    def _eager_judge(self) -> bool:
+        """The eager path's step guard and statistics, with plain torch ops (host syncs are accepted
+        here): per-parameter gradient norms → the global norm → skip or not."""
+        named = [(n, p) for n, p in self.model.named_parameters() if p.requires_grad and p.grad is not None]
+        sq = torch.stack([p.grad.double().pow(2).sum() for _, p in named]) if named else torch.zeros(1, dtype=torch.float64)
+        norm = float(sq.sum().sqrt().float())
+        finite = math.isfinite(norm)
+        h = self._eager_health or {"skipped": 0, "consecutive": 0, "last_norm": 0.0, "last_finite_norm": 0.0,
+                                   "last_skipped_step": 0}
+        h["last_norm"] = norm
+        skip = self.skip_nonfinite_steps and not finite
+        if skip:
+            h["skipped"] += 1
+            h["consecutive"] += 1
+            h["last_skipped_step"] = self.global_step + 1
+        else:
+            h["consecutive"] = 0
+            if finite:
+                h["last_finite_norm"] = norm
+        self._eager_health = h
+        if skip or (self.track_grad_norm is not None and self._log_step_next()):
+            rows = torch.tensor([[float(s.sqrt()), float(p.detach().double().norm()),
+                                  float(torch.where(torch.isnan(p.grad), torch.zeros_like(p.grad), p.grad.abs()).max())
+                                  if p.grad.numel() else 0.0, float((~torch.isfinite(p.grad)).sum())]
+                                 for s, (_, p) in zip(sq, named)], dtype=torch.float32).reshape(-1, 4)
+            old = self._eager_stats or ([], None, None)
+            self._eager_stats = ([n for n, _ in named], rows if not skip or self._log_step_next() else old[1],
+                                 rows if skip else old[2])
+        return skip
 
     @torch.no_grad()
     def _run_eval(self, dl, stage: str, limit: Optional[int] = None, swap: bool = True) -> Dict[str, float]:
@@ -635,11 +769,27 @@ class Trainer:
 
 
 _KNOWN_NOOP = {"process_position", "auto_select_gpus", "tpu_cores", "ipus", "log_gpu_memory",
-               "progress_bar_refresh_rate", "track_grad_norm", "flush_logs_every_n_steps", "sync_batchnorm",
+               "progress_bar_refresh_rate", "flush_logs_every_n_steps", "sync_batchnorm",
                "enable_model_summary", "weights_summary", "weights_save_path", "reload_dataloaders_every_n_epochs",
                "reload_dataloaders_every_epoch", "auto_lr_find", "auto_scale_batch_size", "prepare_data_per_node",
                "plugins", "amp_backend", "amp_level", "move_metrics_to_cpu", "multiple_trainloader_mode",
                "stochastic_weight_avg", "limit_predict_batches", "min_epochs", "max_time"}
+
+
+def _norm_type(v):
+    """``track_grad_norm``: -1 (Lightning's default) / None = off → None; 2 → 2.0; "inf" → inf."""
+    if v is None or v is False:
+        return None
+    try:
+        f = float(v)
+    except (TypeError, ValueError):
+        f = float("nan")
+    if f == -1:
+        return None
+    if f == 2.0 or f == float("inf"):
+        return f
+    raise ValueError(f"track_grad_norm must be -1 (off), 2 or 'inf' (the norms the fused statistics provide), "
+                     f"got {v!r}")
 
 
 def _batch_size(batch) -> int:
