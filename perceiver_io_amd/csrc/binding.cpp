@@ -22,13 +22,15 @@ hipStream_t stream() { return at::hip::getCurrentHIPStream(); }
 // checked builds: the device error words of every checked translation unit (bit 1: a token id
 // outside the embedding table, 2: a gather row outside its destination, 4: a class label
 // outside [0, V) ∪ {-100}, 8: a PE row index outside its table, 16: a batch_augment crop box that had to be
-// clamped into its source image, 32: a rand_augment op word outside its table); reset clears them
+// clamped into its source image, 32: a rand_augment op word outside its table, 128: an event_compact
+// dihedral code outside 0-7); reset clears them
 int64_t check_errors(bool reset) {
   return (int64_t)(pio::check_errors_elementwise(reset) | pio::check_errors_optim(reset) |
                    pio::check_errors_mlm_head(reset) | pio::check_errors_ce_head(reset) | pio::check_errors_topk_head(reset) |
                    pio::check_errors_rowgemm(reset) | pio::check_errors_pixel_head(reset) |
                    pio::check_errors_soft_ce_head(reset) | pio::check_errors_augment(reset) |
-                   pio::check_errors_randaugment(reset) | pio::check_errors_health(reset));
+                   pio::check_errors_randaugment(reset) | pio::check_errors_health(reset) |
+                   pio::check_errors_lartpc_prep(reset));
 }
 bool checked_build() { return PIO_CHECKS != 0; }
 // checked builds, outside graph capture: wait for the kernel just launched and raise on any
@@ -1835,6 +1837,52 @@ std::vector<Tensor> nonzero_compact(Tensor img, int64_t cap, int64_t segs, int64
   return {values, index, kmask, count};
 }
 
+// img (B, H, W) fp32, lab (B, H·W) uint8, words (B) int32 (one dihedral code per sample, read on
+// the device) → [values (B, key_cap, 1), index (B, key_cap) int64, kmask (B, key_cap) bool,
+// qidx (B, query_cap) int64, qlab (B, query_cap) int64, counts (B, 2) int32] in the flat order of
+// the transformed event (lartpc_prep.hip).  wmask: bit c set when class c < ncls is weighted.
+// Non-square planes are refused: a transposing word, which the host cannot see, needs H == W.
+// Capacities 0 only count.  segs / tile as in nonzero_compact.
+std::vector<Tensor> event_compact(Tensor img, Tensor lab, Tensor words, int64_t key_cap, int64_t query_cap, int64_t wmask,
+                                  int64_t ncls, int64_t segs, int64_t tile) {
+  CHECK_CUDA(img); CHECK_CUDA(lab); CHECK_CUDA(words);
+  CHECK_DT(img, torch::kFloat32); CHECK_DT(lab, torch::kUInt8); CHECK_DT(words, torch::kInt32);
+  TORCH_CHECK(img.dim() == 3 && img.is_contiguous(), "event_compact: img must be (B, H, W) contiguous");
+  const int64_t B = img.size(0), H = img.size(1), W = img.size(2), npix = H * W;
+  TORCH_CHECK(H == W, "event_compact: the device path needs square planes (a transposing code needs H == W), got ", H, " x ", W);
+  TORCH_CHECK(B > 0 && B <= 65535 && npix > 0 && npix < (1ll << 31) && key_cap >= 0 && query_cap >= 0,
+              "event_compact: bad shape or capacity");
+  TORCH_CHECK(lab.dim() == 2 && lab.size(0) == B && lab.size(1) == npix && lab.is_contiguous(),
+              "event_compact: lab must be (B, H*W) contiguous");
+  TORCH_CHECK(words.dim() == 1 && words.size(0) == B && words.is_contiguous(), "event_compact: words must be (B,) contiguous");
+  TORCH_CHECK(lab.get_device() == img.get_device() && words.get_device() == img.get_device(),
+              "event_compact: img, lab and words must share a device");
+  TORCH_CHECK(ncls >= 1 && ncls <= 8 && wmask >= 0 && wmask < (1ll << ncls), "event_compact: at most 8 classes, wmask inside them");
+  TORCH_CHECK(segs >= 0 && segs <= 256 && (tile == 0 || tile == 4 || tile == 8), "event_compact: segs in [0, 256], tile in {0, 4, 8}");
+  const int V = tile == 0 ? kNonzeroTile : (int)tile;
+  int S = (int)segs;
+  if (S == 0) S = (int)std::min<int64_t>(kNonzeroSegs, (npix + 256 * V - 1) / (256 * V));
+  auto i64 = img.options().dtype(torch::kInt64), i32 = img.options().dtype(torch::kInt32);
+  Tensor values = torch::empty({B, key_cap, 1}, img.options()), index = torch::empty({B, key_cap}, i64);
+  Tensor kmask = torch::empty({B, key_cap}, img.options().dtype(torch::kBool));
+  Tensor qidx = torch::empty({B, query_cap}, i64), qlab = torch::empty({B, query_cap}, i64);
+  Tensor counts = torch::empty({B, 2}, i32);
+  Tensor segcount;
+  if (S > 1) segcount = torch::empty({B, S, 2}, i32);
+  pio::EventCompactArgs a{};
+  a.img = f32p(img); a.lab = lab.data_ptr<uint8_t>(); a.words = words.data_ptr<int>();
+  a.B = (int)B; a.H = (int)H; a.W = (int)W;
+  a.kcap = key_cap; a.qcap = query_cap;
+  a.wmask = (unsigned)wmask; a.ncls = (int)ncls;
+  a.S = S; a.V = V;
+  a.segcount = S > 1 ? segcount.data_ptr<int>() : nullptr;
+  a.values = values.data_ptr<float>(); a.index = index.data_ptr<int64_t>(); a.kmask = kmask.data_ptr<bool>();
+  a.qidx = qidx.data_ptr<int64_t>(); a.qlab = qlab.data_ptr<int64_t>(); a.counts = counts.data_ptr<int>();
+  pio::event_compact_launch(a, stream());
+  checked_sync("event_compact");
+  return {values, index, kmask, qidx, qlab, counts};
+}
+
 // ---- the flat-space optimizers (csrc/optim.hip, lamb.hip, ema.hip): one set of argument checks ----
 namespace {
 bool aligned(const void* q, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(q) & (bytes - 1)) == 0; }
@@ -2461,6 +2509,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("pixel_predict", &pixel_predict, py::arg("h"), py::arg("w"), py::arg("b"), py::arg("qidx"), py::arg("qvalid"),
         py::arg("Q"), py::arg("npix"), py::arg("labels") = py::none());
   m.def("nonzero_compact", &nonzero_compact, py::arg("img"), py::arg("cap"), py::arg("segs") = 0, py::arg("tile") = 0);
+  m.def("event_compact", &event_compact, py::arg("img"), py::arg("lab"), py::arg("words"), py::arg("key_cap"),
+        py::arg("query_cap"), py::arg("wmask"), py::arg("ncls"), py::arg("segs") = 0, py::arg("tile") = 0);
   m.def("stage_step", &stage_step, py::arg("dsts"), py::arg("srcs"), py::arg("hyper_dst") = py::none(),
         py::arg("hyper") = std::vector<double>{}, py::arg("seed_dst") = py::none(),
         py::arg("seeds") = std::vector<int64_t>{});

@@ -26,7 +26,7 @@ namespace pio {
 #define PIO_CHECKS 0
 #endif
 enum : unsigned { kErrEmbedId = 1u, kErrGatherRow = 2u, kErrLabel = 4u, kErrPeIndex = 8u, kErrAugmentBox = 16u,
-                  kErrRandAugOp = 32u, kErrOptTable = 64u };
+                  kErrRandAugOp = 32u, kErrOptTable = 64u, kErrDihedral = 128u };
 static __device__ unsigned pio_errors;
 __device__ __forceinline__ void pio_flag(unsigned bit) {
 #if PIO_CHECKS

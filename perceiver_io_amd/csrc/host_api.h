@@ -375,6 +375,32 @@ void lamb_launch(float* p, float* g, float* m, float* v, uint16_t* shadow, long 
                  float* trust, float eps, float clip, float gscale, int zero_g, const float* loss_src,
                  float* loss_ring, int ring_n, const float* norm_part, const int* tgroup, int G, const float* guard,
                  hipStream_t st);
+// ---- lartpc_prep.hip ----
+// event_compact: img (B, H, W) fp32, lab (B, H·W) uint8 and one dihedral code per sample in words
+// (B) int32, all on the device → keys (values / index / kmask, kcap slots per sample), queries
+// (qidx / qlab, qcap slots) and counts (B, 2) in the flat order of the transformed event.  wmask:
+// bit c set when class c < ncls <= 8 is weighted.  H == W, H·W < 2^31; S in [1, 256] segments per
+// sample, V in {4, 8} loads per thread and tile; segcount: (B, S, 2) int32 scratch (unused when
+// S == 1)
+struct EventCompactArgs {
+  const float* img;
+  const uint8_t* lab;
+  const int* words;
+  int B, H, W;
+  long long kcap, qcap;
+  unsigned wmask;
+  int ncls;
+  int S, V;
+  int* segcount;
+  float* values;
+  int64_t* index;
+  bool* kmask;
+  int64_t* qidx;
+  int64_t* qlab;
+  int* counts;
+};
+void event_compact_launch(const EventCompactArgs& a, hipStream_t st);
+unsigned check_errors_lartpc_prep(bool reset);
 // ---- mlm_head.hip ----
 void mlm_select_launch(const int64_t* labels, int B, int L, int cap, int gcap, int64_t* idx_b, int64_t* lab_b,
                        int* count, int64_t* gidx, int64_t* glab, float* total, bool* overflow, bool* sticky,

@@ -16,6 +16,7 @@
 // per-sample class map and an optional confusion count, and nonzero_compact — the device-side
 // sparsifier that turns a dense image into the encoder's (values, index, kmask) operands.
 #include "common.h"
+#include "compact.h"
 
 namespace pio {
 
@@ -387,14 +388,6 @@ void pixel_predict_launch(int C, int K, const float* H, const float* W, const fl
 // a ping-pong LDS buffer (one barrier per tile), the running base in a register of every thread.
 // The order comes from the scan alone (no atomics).  With S = 1 the count launch is skipped; a
 // counting call (cap = 0) with S > 1 skips the walk instead (its total is the sum of the counts).
-constexpr int NZ_THREADS = 256, NZ_WAVES = NZ_THREADS / 64;
-
-__device__ __forceinline__ int wave_isum(int v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(NZ_THREADS) void nonzero_count_kernel(const float* __restrict__ img, long long npix,
                                                                    long long seg, int* __restrict__ segcount) {
   const int s = blockIdx.x, b = blockIdx.y, S = gridDim.x;
@@ -402,11 +395,9 @@ __global__ __launch_bounds__(NZ_THREADS) void nonzero_count_kernel(const float* 
   const float* p = img + (long long)b * npix;
   int n = 0;
   for (long long i = start + threadIdx.x; i < end; i += NZ_THREADS) n += p[i] != 0.f ? 1 : 0;
-  n = wave_isum(n);
   __shared__ int sW[NZ_WAVES];
-  if (lane_id() == 0) sW[wave_id()] = n;
-  __syncthreads();
-  if (threadIdx.x == 0) segcount[(long long)b * S + s] = sW[0] + sW[1] + sW[2] + sW[3];
+  n = block_isum(n, sW);
+  if (threadIdx.x == 0) segcount[(long long)b * S + s] = n;
 }
 
 template <int V>
@@ -418,58 +409,38 @@ __global__ __launch_bounds__(NZ_THREADS) void nonzero_scatter_kernel(const float
                                                                      bool* __restrict__ kmask, int* __restrict__ count) {
   constexpr int TILE = NZ_THREADS * V;
   const int s = blockIdx.x, b = blockIdx.y, S = gridDim.x;
-  const int l = lane_id(), w = wave_id();
   __shared__ int sW[2][V][NZ_WAVES];
   __shared__ int sR[2][NZ_WAVES];
   long long run = 0, total = 0;  // slots of the sample before this block's next tile; the sample's count
-  if (S > 1) {                   // S <= NZ_THREADS: one segment count per thread
-    const int c = (int)threadIdx.x < S ? segcount[(long long)b * S + threadIdx.x] : 0;
-    const int before = wave_isum((int)threadIdx.x < s ? c : 0), all = wave_isum(c);
-    if (l == 0) { sR[0][w] = before; sR[1][w] = all; }
-    __syncthreads();
-    run = sR[0][0] + sR[0][1] + sR[0][2] + sR[0][3];
-    total = sR[1][0] + sR[1][1] + sR[1][2] + sR[1][3];
-  }
+  if (S > 1) seg_prefix(segcount + (long long)b * S, 1, s, S, sR, run, total);  // S <= NZ_THREADS
   const long long start = (long long)s * seg, end = start + seg < npix ? start + seg : npix;
   const float* p = img + (long long)b * npix;
   float* vo = values + (long long)b * cap;
   int64_t* io = index + (long long)b * cap;
   bool* mo = kmask + (long long)b * cap;
-  const uint64_t below = (1ull << l) - 1ull;
   int buf = 0;
   // a counting call (cap == 0) with S > 1 already has its total: no second read of the image
   const bool walk = S == 1 || cap > 0;
   for (long long t0 = start; walk && t0 < end; t0 += TILE, buf ^= 1) {
     float v[V];
+    bool hit[V];
     int pre[V];
 #pragma unroll
     for (int j = 0; j < V; ++j) {
       const long long i = t0 + j * NZ_THREADS + threadIdx.x;
       v[j] = i < end ? p[i] : 0.f;
+      hit[j] = v[j] != 0.f;
     }
-#pragma unroll
-    for (int j = 0; j < V; ++j) {
-      const uint64_t m = __ballot(v[j] != 0.f);
-      pre[j] = __popcll(m & below);
-      if (l == 0) sW[buf][j][w] = __popcll(m);
-    }
+    tile_ballot<V>(hit, pre, sW[buf]);
     lds_sync();
 #pragma unroll
     for (int j = 0; j < V; ++j) {
-      int woff = 0, tot = 0;
-#pragma unroll
-      for (int k = 0; k < NZ_WAVES; ++k) {
-        const int c = sW[buf][j][k];
-        woff += k < w ? c : 0;
-        tot += c;
-      }
-      const long long pos = run + woff + pre[j];
-      if (v[j] != 0.f && pos < cap) {
+      const long long pos = tile_slot(sW[buf][j], pre[j], run);
+      if (hit[j] && pos < cap) {
         vo[pos] = v[j];
         io[pos] = t0 + j * NZ_THREADS + threadIdx.x;
         mo[pos] = false;
       }
-      run += tot;
     }
   }
   if (S == 1) total = run;
@@ -483,17 +454,11 @@ __global__ __launch_bounds__(NZ_THREADS) void nonzero_scatter_kernel(const float
   if (s == 0 && threadIdx.x == 0) count[b] = (int)total;
 }
 
-// pixels per segment for S segments: whole tiles of 256·V
-long long nonzero_seg_len(long long npix, int S, int V) {
-  const long long tile = (long long)NZ_THREADS * V, per = (npix + S - 1) / S;
-  return (per + tile - 1) / tile * tile;
-}
-
 // S in [1, 256] segments per sample, V in {4, 8} loads per thread and tile; segcount: (B, S) int32
 // scratch (unused when S == 1)
 void nonzero_compact_launch(const float* img, int B, long long npix, long long cap, int S, int V, int* segcount,
                             float* values, int64_t* index, bool* kmask, int* count, hipStream_t st) {
-  const long long seg = nonzero_seg_len(npix, S, V);
+  const long long seg = compact_seg_len(npix, S, V);
   const dim3 g(S, B), t(NZ_THREADS);
   if (S > 1) hipLaunchKernelGGL(nonzero_count_kernel, g, t, 0, st, img, npix, seg, segcount);
   if (V == 8)

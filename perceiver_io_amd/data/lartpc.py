@@ -15,11 +15,17 @@ distinct shapes, so the step engine keeps one captured hipGraph per shape.
 For inference the key tensors are built on the device instead: the ``nonzero_compact`` kernel
 (``LArPerceiver.segment``) returns, at the same capacity, bitwise the ``values / index / kmask``
 of ``sparse_collate`` from a dense image batch that is already on the GPU.
+
+Training can build the whole batch there (``run.py --device-collate``): ``DenseCollator`` only
+stacks the events (fp32 image, uint8 labels), ``DihedralAugment.draw`` adds one int32 code per
+sample, and ``ops.event_compact`` (``LArPerceiver.event_loss``) produces all five tensors at fixed
+capacities inside the step, read through the flip / 90° turn the code names.
 """
 from __future__ import annotations
 
 from typing import List, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from ..models.lartpc import CLASS_WEIGHTS
@@ -68,3 +74,46 @@ class SparseCollator:
 
     def __call__(self, events):
         return sparse_collate(events, self.bucket, self.weights)
+
+
+class DenseCollator:
+    """Picklable ``collate_fn`` of the device path: ``(img (B, H, W) fp32, lab (B, H·W) uint8)``.
+    Nothing is searched or compacted on the host; labels travel as bytes."""
+
+    def __call__(self, events):
+        img = torch.stack([e[0] for e in events]).float()
+        lab = torch.stack([e[1].reshape(-1) for e in events]).to(torch.uint8)
+        return img, lab
+
+
+DIHEDRAL_MODES = ("dihedral", "flip", "none")
+
+
+class DihedralAugment:
+    """Flips and 90° turns of a wire-plane event, as one code per sample for
+    ``ops.event_compact``: bit 2 transposes (applied first), bit 0 mirrors the columns, bit 1 the
+    rows.  ``dihedral`` draws all eight symmetries of the square, ``flip`` bits 0–1 only (the four
+    that exist for a non-square plane), ``none`` always 0."""
+
+    def __init__(self, mode: str = "dihedral"):
+        if mode not in DIHEDRAL_MODES:
+            raise ValueError(f"mode must be one of {DIHEDRAL_MODES}, got {mode!r}")
+        self.mode = mode
+
+    @staticmethod
+    def rng(seed: int = 0, rank: int = 0) -> np.random.Generator:
+        return np.random.default_rng([int(seed), int(rank)])
+
+    def draw(self, rng: np.random.Generator, B: int, train: bool = True) -> np.ndarray:
+        """One int32 code per sample; ``train=False`` (evaluation): all zeros."""
+        if not train or self.mode == "none":
+            return np.zeros(B, dtype=np.int32)
+        return rng.integers(0, 8 if self.mode == "dihedral" else 4, size=B).astype(np.int32)
+
+    @staticmethod
+    def apply_host(img: torch.Tensor, lab: torch.Tensor, code: int):
+        """The transform on the host: ``(img (H, W), lab (H·W,))`` → the same pair under ``code``."""
+        from ..ops.emulation import dihedral
+
+        h, w = img.shape
+        return dihedral(img, code).contiguous(), dihedral(lab.reshape(h, w), code).reshape(-1).contiguous()

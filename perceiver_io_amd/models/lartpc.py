@@ -126,6 +126,22 @@ class LArPerceiver(torch.nn.Module):
         h = self.sparse_hidden(values, index, kmask, qidx)
         return pixel_ce(h, self.perceiver.decoder.output_adapter.linear, qlab, weights)
 
+    def event_loss(self, batch, weights: torch.Tensor, key_capacity: int, query_capacity: int,
+                   class_weights: Sequence[float] = CLASS_WEIGHTS):
+        """``(loss, {acc, acc1, acc2}, counts)`` for dense events ``batch = (img (B, H, W) fp32, lab
+        (B, H·W) uint8, words (B,) int32)``: ``ops.event_compact`` builds the sparse batch on the
+        batch's device, each sample under the dihedral code in ``words``, and :meth:`sparse_loss`
+        takes it from there.  ``class_weights`` is the host copy of ``weights`` (which pixels are
+        queries is decided without reading the device).  Shapes depend on the capacities alone, so
+        one captured graph serves every batch.  Pixels past a capacity are left out of the loss, as
+        in ``segment(capacity=)``; ``counts`` (B, 2) int32 holds the true key and query counts, so
+        the caller can see that."""
+        from .. import ops
+
+        img, lab, words = batch
+        *sparse, counts = ops.event_compact(img, lab, words, int(key_capacity), int(query_capacity), class_weights)
+        loss, acc = self.sparse_loss(tuple(sparse), weights)
+        return loss, acc, counts
 
     def segment_sparse(self, values, index, kmask, qidx=None, qmask=None, labels=None) -> Segmentation:
         """Class map of a sparse batch (``sparse_collate`` layout, or :func:`nonzero_compact`'s).

@@ -73,7 +73,9 @@ def check_device_errors(reset: bool = True) -> None:
       call itself never raises for it), bit 32: a ``rand_augment`` op word outside its table
       (applied as identity), and bit 64: a chunk of ``adamw_grouped`` outside the flat buffers, or
       a group id of ``adamw_grouped`` / ``lamb(tensor_group=)`` outside the optimizer's groups (the
-      chunk is skipped; ``lamb`` skips a chunk outside the buffers without flagging it).
+      chunk is skipped; ``lamb`` skips a chunk outside the buffers without flagging it), and bit
+      128: an ``event_compact`` dihedral code outside 0–7 (applied as identity; a label at or past
+      the class count raises bit 4 and is not selected).
       Outside a graph capture every checked launch raises at once (``checked_sync``); inside a
       replayed hipGraph nothing can.
 
@@ -99,7 +101,8 @@ def check_device_errors(reset: bool = True) -> None:
                                "8 PE row index outside the position-encoding table, "
                                "16 batch_augment crop box outside its source image, "
                                "32 rand_augment op word outside its table, "
-                               "64 adamw_grouped chunk outside the flat buffers, or an optimizer group id outside its groups)")
+                               "64 adamw_grouped chunk outside the flat buffers, or an optimizer group id outside its groups, "
+                               "128 event_compact dihedral code outside 0-7)")
 
 
 def use_hip(t: torch.Tensor) -> bool:
@@ -186,6 +189,44 @@ def rand_augment(src: torch.Tensor, words: torch.Tensor, fill: int = 0) -> torch
     from . import emulation
 
     return emulation.rand_augment(src, words, int(fill))
+
+
+def event_compact(img: torch.Tensor, lab: torch.Tensor, words: torch.Tensor, key_cap: int, query_cap: int, weights):
+    """Dense LArTPC events → the sparse training batch of ``data.lartpc.sparse_collate`` at fixed
+    capacities, read through one dihedral symmetry per sample.
+
+    ``img`` (B, H, W) fp32, ``lab`` (B, H·W) uint8 and ``words`` (B,) int32 live on one device.  Code
+    bits: 4 transposes first ((i', j') = (j, i)), 1 mirrors the columns (j' = W − 1 − j'), 2 the rows
+    (i' = H − 1 − i'), where output pixel (i, j) takes source pixel (i', j'); a code outside 0–7 is
+    the identity (the checked build flags it).  ``weights``: the class weights as a Python sequence
+    of at most 8 floats; a pixel is a query when its label's weight is non-zero.  Returns ``(values
+    (B, key_cap, 1), index (B, key_cap) int64, kmask (B, key_cap) bool, qidx (B, query_cap) int64,
+    qlab (B, query_cap) int64, counts (B, 2) int32)`` in the flat order of the transformed event,
+    padded exactly like ``sparse_collate``; ``counts`` holds the true key and query counts, also
+    beyond the capacities (capacities 0 only count).
+
+    HIP path: ``csrc/lartpc_prep.hip`` reads ``words`` from device memory — no host sync, and a
+    replayed hipGraph transforms with whatever words were staged for that step.  Because the host
+    never sees the words, it refuses non-square planes outright: a transposing code needs H == W.
+    The emulation (CPU) takes non-square planes and raises only when a word transposes."""
+    weights = tuple(float(w) for w in weights)
+    if not 1 <= len(weights) <= 8:
+        raise ValueError(f"event_compact: 1 to 8 class weights, got {len(weights)}")
+    if img.dim() != 3 or lab.shape != (img.shape[0], img.shape[1] * img.shape[2]) or lab.dtype != torch.uint8:
+        raise ValueError(f"event_compact: img (B, H, W) and lab (B, H*W) uint8, got {tuple(img.shape)} and "
+                         f"{tuple(lab.shape)} {lab.dtype}")
+    if words.shape != (img.shape[0],):
+        raise ValueError(f"event_compact: words must be (B,), got {tuple(words.shape)}")
+    wmask = sum(1 << c for c, w in enumerate(weights) if w != 0)
+    if use_hip(img):
+        if img.shape[1] != img.shape[2]:
+            raise ValueError(f"event_compact: the device path needs square planes, got {tuple(img.shape[1:])}")
+        x = img if img.dtype == torch.float32 and img.is_contiguous() else img.float().contiguous()
+        w = words.to(device=img.device, dtype=torch.int32).contiguous()
+        return tuple(ext.require().event_compact(x, lab.contiguous(), w, int(key_cap), int(query_cap), wmask, len(weights)))
+    from . import emulation
+
+    return tuple(emulation.event_compact(img.float(), lab, words, int(key_cap), int(query_cap), wmask, len(weights)))
 
 
 from . import attention, fused, masking, mlm_head, optim  # noqa: E402,F401

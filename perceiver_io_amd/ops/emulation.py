@@ -1237,6 +1237,55 @@ def nonzero_compact(img, cap, segs=0, tile=0):
     return [values.unsqueeze(-1), index, kmask, count.to(torch.int32)]
 
 
+def dihedral(plane, code: int):
+    """``plane`` (H, W) under dihedral code ``code``: output pixel (i, j) takes source pixel
+    (i', j') with bit 2 (first) (i', j') = (j, i), bit 0 j' = W − 1 − j', bit 1 i' = H − 1 − i'.  A
+    code outside 0–7 is the identity; a transposing code needs a square plane."""
+    code = int(code)
+    if not 0 <= code <= 7:
+        code = 0
+    if code & 4 and plane.shape[0] != plane.shape[1]:
+        raise ValueError(f"dihedral code {code} transposes: the plane must be square, got {tuple(plane.shape)}")
+    # out = flips(src)ᵀ: the flips act on the source axes, the transposition on the result
+    if code & 1:
+        plane = plane.flip(1)
+    if code & 2:
+        plane = plane.flip(0)
+    if code & 4:
+        plane = plane.transpose(0, 1)
+    return plane
+
+
+def event_compact(img, lab, words, key_cap, query_cap, wmask, ncls=8, segs=0, tile=0):
+    """[values (B, key_cap, 1), index (B, key_cap) int64, kmask (B, key_cap) bool, qidx (B,
+    query_cap) int64, qlab (B, query_cap) int64, counts (B, 2) int32] of lartpc_prep.hip
+    ``event_compact``: ``img`` (B, H, W) and ``lab`` (B, H·W) uint8 under the per-sample dihedral
+    code ``words`` (B,), then :func:`nonzero_compact` for the keys (``img != 0``) and the same
+    compaction for the queries (label < 8 with its bit set in ``wmask``), whose padding slot j holds
+    (j mod H·W, −100).  Unlike the kernel's binding this accepts non-square planes as long as no
+    word transposes."""
+    B, H, W = img.shape
+    npix = H * W
+    codes = [int(c) for c in words.reshape(-1).tolist()]
+    timg = torch.stack([dihedral(img[b], codes[b]) for b in range(B)]).reshape(B, npix)
+    tlab = torch.stack([dihedral(lab[b].reshape(H, W), codes[b]) for b in range(B)]).reshape(B, npix)
+    values, index, kmask, kcount = nonzero_compact(timg, key_cap)
+    l64 = tlab.long()
+    weighted = torch.tensor([bool((int(wmask) >> c) & 1) for c in range(8)], device=img.device)
+    sel = (l64 < 8) & weighted[l64.clamp(max=7)]
+    qcount = sel.sum(1)
+    pos = torch.cumsum(sel, 1) - 1
+    keep = sel & (pos < query_cap)
+    qidx = (torch.arange(query_cap, device=img.device) % npix).repeat(B, 1)
+    qlab = torch.full((B, query_cap), -100, dtype=torch.long, device=img.device)
+    bi, pi = torch.nonzero(keep, as_tuple=True)
+    slot = pos[bi, pi]
+    qidx[bi, slot] = pi
+    qlab[bi, slot] = l64[bi, pi]
+    counts = torch.stack([kcount, qcount.to(torch.int32)], 1)
+    return [values, index, kmask, qidx, qlab, counts]
+
+
 # ---- per-sample latent-block kernels (csrc/sample_block.hip): 32 latents, 4 heads -------------
 # the same operands, bf16 rounding points and outputs as sb_fwd / sb_bwd / sb_wgrad
 _SB_N, _SB_H = 32, 4

@@ -21,6 +21,14 @@ On a GPU the default is the MI355X path:
   flight.  The reference steps it on the current loss; with patience 5000 the one-step lag
   changes nothing in practice.
 
+``--device-collate`` moves batch building onto the device (``LArPerceiver.event_loss``): the
+loaders only stack dense events (fp32 image, uint8 labels), and ``ops.event_compact`` builds the
+sparse batch inside the step at fixed capacities, so training captures exactly one graph.
+``--augment {flip,dihedral}`` adds flips and 90° turns for free: one int32 code per sample is drawn
+on the host and the compaction reads the pixels through it (validation runs code 0).  Unset
+``--key-capacity`` / ``--query-capacity`` are sized by one counting pass over both loaders.  Pixels
+past a capacity are dropped from the loss, and every log step that sees an overflow says so.
+
 ``--engine eager`` (the default on CPU) runs the reference sequence exactly: zero_grad,
 forward, ``scheduler.step(loss)``, backward, ``clip_grad_norm_``, ``Adam.step``.
 
@@ -31,6 +39,7 @@ tfevents/JSONL.  With the fused optimizer, ``optimizer_state_dict`` covers the t
 parameters.  The unused U-ResNet never has a gradient, and torch's Adam skips it too.
 
     python run.py [--epochs 10] [--events 64] [--size 512] [--batch-size 4] [--dense] [--engine eager]
+    python run.py --device-collate --augment dihedral [--key-capacity K] [--query-capacity Q]
 
 ``--segment CKPT --out DIR`` trains nothing: it loads ``model_state_dict`` from the checkpoint,
 segments the validation events through ``LArPerceiver.segment`` (sparse, no dense logits) and
@@ -45,12 +54,13 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from perceiver_io_amd.data.lartpc import SparseCollator  # noqa: E402
+from perceiver_io_amd.data.lartpc import DenseCollator, DihedralAugment, SparseCollator, _round_up  # noqa: E402
 from perceiver_io_amd.data.synthetic import SyntheticLArTPC  # noqa: E402
 from perceiver_io_amd.models.lartpc import LArPerceiver, accuracies, class_weights, iou  # noqa: E402
 from perceiver_io_amd.train.loggers import TensorBoardLogger  # noqa: E402
@@ -79,6 +89,46 @@ def make_step_fn(model, weights, sparse: bool, metrics: dict):
     return loss_fn
 
 
+def make_event_step_fn(model, weights, caps, metrics: dict, side: dict):
+    """loss_fn((img, lab, words)) → loss of ``--device-collate``; accuracies land in ``metrics``, the
+    batch's true key / query counts (B, 2) in ``side`` (device tensors)."""
+
+    def loss_fn(batch):
+        loss, acc, counts = model.event_loss(batch, weights, caps[0], caps[1])
+        metrics.update(acc)
+        side["counts"] = counts
+        return loss
+
+    return loss_fn
+
+
+def size_capacities(loaders, dev, bucket: int):
+    """One counting pass (``event_compact`` with capacities 0) over ``loaders``: the largest key and
+    query count of any event, kept on the device and read once, rounded up to ``bucket``."""
+    from perceiver_io_amd import ops
+    from perceiver_io_amd.models.lartpc import CLASS_WEIGHTS
+
+    top = torch.zeros(2, dtype=torch.int32, device=dev)
+    for loader in loaders:
+        for img, lab in loader:
+            words = torch.zeros(img.shape[0], dtype=torch.int32, device=dev)
+            counts = ops.event_compact(img.to(dev), lab.to(dev), words, 0, 0, CLASS_WEIGHTS)[5]
+            top = torch.maximum(top, counts.max(0).values)
+    k, q = top.tolist()  # the only read
+    return _round_up(k, bucket), _round_up(q, bucket)
+
+
+def report_overflow(counts, caps, step: int) -> None:
+    """Print the pixels a batch lost to the capacities (never silent)."""
+    k, q = counts.max(0).values.tolist()
+    if k > caps[0] or q > caps[1]:
+        c = counts.long()
+        lost_k = int((c[:, 0] - caps[0]).clamp(min=0).sum())
+        lost_q = int((c[:, 1] - caps[1]).clamp(min=0).sum())
+        print(f"step {step}: capacity overflow, dropped {lost_k} key and {lost_q} query pixels "
+              f"(largest event {k} keys / {q} queries, capacities {caps[0]} / {caps[1]})", flush=True)
+
+
 def segment_events(model, a, dev):
     """``--segment``: ``event_<i>.npy`` (uint8 H×W class map: the class of every non-zero pixel, 0
     elsewhere) for each validation event, and the per-class IoU against the synthetic labels."""
@@ -102,7 +152,7 @@ def segment_events(model, a, dev):
     print("IoU: " + ", ".join(f"{k} {float(v):.4f}" for k, v in zip(names, per)) + f", mean {float(mean):.4f}", flush=True)
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--epochs", type=int, default=10)
     ap.add_argument("--events", type=int, default=64)
@@ -120,10 +170,37 @@ def main(argv=None):
     ap.add_argument("--bucket", type=int, default=2048, help="sparse capacity rounding (keys / queries)")
     ap.add_argument("--log-every", type=int, default=1)
     ap.add_argument("--workers", type=int, default=1)
+    ap.add_argument("--device-collate", action="store_true",
+                    help="build the sparse batch on the device at fixed capacities (one captured graph)")
+    ap.add_argument("--augment", choices=["none", "flip", "dihedral"], default="none",
+                    help="flips / 90-degree turns read through the compaction (needs --device-collate)")
+    ap.add_argument("--key-capacity", type=int, default=None, help="key slots per event (default: counted, rounded to --bucket)")
+    ap.add_argument("--query-capacity", type=int, default=None, help="query slots per event (default: counted)")
+    ap.add_argument("--seed", type=int, default=0, help="seed of the augmentation draws")
     ap.add_argument("--segment", metavar="CKPT", default=None,
                     help="no training: segment the validation events with this checkpoint and write class maps to --out")
     ap.add_argument("--out", metavar="DIR", default="segmented", help="output directory of --segment")
     a = ap.parse_args(argv)
+    if a.augment != "none" and not a.device_collate:
+        ap.error("--augment needs --device-collate")
+    if a.device_collate and a.dense:
+        ap.error("--device-collate builds sparse batches: drop --dense")
+    return a
+
+
+def make_loaders(a):
+    """(train, validation) loaders: the host collator by default, dense stacks with --device-collate."""
+    collate = DenseCollator() if a.device_collate else SparseCollator(a.bucket) if not a.dense else None
+    kw = dict(num_workers=a.workers, persistent_workers=a.workers > 0, collate_fn=collate)
+    train = torch.utils.data.DataLoader(SyntheticLArTPC(a.events, a.size, seed=0), batch_size=a.batch_size,
+                                        shuffle=True, drop_last=True, **kw)
+    val = torch.utils.data.DataLoader(SyntheticLArTPC(a.val_events, a.size, seed=1), batch_size=a.batch_size,
+                                      drop_last=True, collate_fn=collate)
+    return train, val
+
+
+def main(argv=None):
+    a = parse_args(argv)
     dev = torch.device(a.device)
     torch.manual_seed(0)
     model = LArPerceiver(a.size).to(dev)
@@ -131,12 +208,7 @@ def main(argv=None):
         return segment_events(model, a, dev)
     weights = class_weights(dev)
     sparse = not a.dense
-    collate = SparseCollator(a.bucket) if sparse else None
-    kw = dict(num_workers=a.workers, persistent_workers=a.workers > 0, collate_fn=collate)
-    train = torch.utils.data.DataLoader(SyntheticLArTPC(a.events, a.size, seed=0), batch_size=a.batch_size,
-                                        shuffle=True, drop_last=True, **kw)
-    val = torch.utils.data.DataLoader(SyntheticLArTPC(a.val_events, a.size, seed=1), batch_size=a.batch_size,
-                                      drop_last=True, collate_fn=collate)
+    train, val = make_loaders(a)
     fused = dev.type == "cuda" and a.engine != "eager"
     if fused:
         from perceiver_io_amd.ops.optim import FusedAdam
@@ -147,18 +219,36 @@ def main(argv=None):
         opt = torch.optim.Adam(model.parameters(), lr=a.lr, weight_decay=1e-4)
     sched = torch.optim.lr_scheduler.ReduceLROnPlateau(opt, patience=5000, factor=0.1)
     metrics: dict = {}
-    loss_fn = make_step_fn(model, weights, sparse, metrics)
+    side: dict = {}  # --device-collate: the batch's counts, a static output of the captured graph
+    caps, aug, rng = None, None, None
+    if a.device_collate:
+        caps = (a.key_capacity, a.query_capacity)
+        if None in caps:
+            counted = size_capacities((train, val), dev, a.bucket)
+            caps = tuple(c if c is not None else n for c, n in zip(caps, counted))
+        print(f"device collate: {caps[0]} key and {caps[1]} query slots per event, augment {a.augment}", flush=True)
+        aug, rng = DihedralAugment(a.augment), DihedralAugment.rng(a.seed, 0)
+        loss_fn = make_event_step_fn(model, weights, caps, metrics, side)
+    else:
+        loss_fn = make_step_fn(model, weights, sparse, metrics)
+
+    def with_words(batch, training: bool):
+        if aug is None:
+            return batch
+        return (*batch, torch.from_numpy(aug.draw(rng, batch[0].shape[0], training)))
+
     engine = None
     if fused:
         engine = StepEngine(loss_fn, opt, None, device=dev, graph=True,
-                            state_hooks=(lambda: dict(metrics), lambda s: metrics.update(s)))
+                            state_hooks=(lambda: (dict(metrics), dict(side)),
+                                         lambda s: (metrics.update(s[0]), side.update(s[1]))))
     log = TensorBoardLogger(a.log_dir, name="lartpc")
     step, epoch, prev = 0, 0, None
     t_start, n_timed = None, 0
     for epoch in range(a.epochs):
         model.train()
         for batch in train:
-            batch = _to(batch, dev)
+            batch = _to(with_words(batch, True), dev)
             t0 = time.perf_counter()
             if fused:
                 loss = engine.step(batch)
@@ -184,6 +274,8 @@ def main(argv=None):
                                  **{f"train_{k}": v for k, v in vals.items()}}, step)
                 print(f"epoch {epoch} step {step} loss {float(loss):.4f} acc {vals.get('acc', 0):.3f} "
                       f"{time.perf_counter() - t0:.3f}s", flush=True)
+                if caps is not None:
+                    report_overflow(side["counts"], caps, step)
             step += 1
             if 0 < a.max_steps <= step:
                 break
@@ -191,9 +283,12 @@ def main(argv=None):
         vl, va = [], []
         with torch.no_grad():
             for batch in val:
-                batch = _to(batch, dev)
+                batch = _to(with_words(batch, False), dev)
                 vm: dict = {}
-                vl.append(float(make_step_fn(model, weights, sparse, vm)(batch)))
+                if caps is not None:
+                    vl.append(float(make_event_step_fn(model, weights, caps, vm, {})(batch)))
+                else:
+                    vl.append(float(make_step_fn(model, weights, sparse, vm)(batch)))
                 va.append(float(vm["acc"]))
         if vl:
             log.log_metrics({"validation_loss": sum(vl) / len(vl), "val_acc": sum(va) / len(va)}, step)
@@ -204,7 +299,10 @@ def main(argv=None):
         if dev.type == "cuda":
             torch.cuda.synchronize()
         print(f"throughput: {n_timed / (time.perf_counter() - t_start):.1f} samples/s "
-              f"({'sparse' if sparse else 'dense'}, {'fused graph' if fused else 'eager'})", flush=True)
+              f"({'sparse' if sparse else 'dense'}, {'fused graph' if fused else 'eager'}"
+              f"{', device collate' if caps is not None else ''})", flush=True)
+    if engine is not None and caps is not None:
+        print(f"captured training graphs: {engine.num_graphs}", flush=True)
     os.makedirs(a.ckpt_dir, exist_ok=True)
     torch.save({"epoch": epoch, "model_state_dict": model.state_dict(), "optimizer_state_dict": opt.state_dict()},
                os.path.join(a.ckpt_dir, f"model_{epoch}.ckpt"))
