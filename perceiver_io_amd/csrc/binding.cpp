@@ -1552,6 +1552,101 @@ Tensor embed_fwd(Tensor ids, Tensor E, Tensor P, double scale) {
   return out;
 }
 
+// The text encoder's input pass: the embedding and both cross layers' LayerNorm + K|V projection
+// in one launch.  la / lb = [lnw (64), lnb (64), w bf16 (128, 64), bias (128)] of layer_1 /
+// layer_n; returns (x (B, L, 64) fp32, mean, rstd, kv_a, kv_b (B·L, 128) bf16).
+std::vector<Tensor> text_kv_fwd(Tensor ids, Tensor E, Tensor P, double scale, double eps, std::vector<Tensor> la,
+                                std::vector<Tensor> lb) {
+  CHECK_CUDA(ids); CHECK_CUDA(E);
+  TORCH_CHECK(ids.dim() == 2 && ids.is_contiguous() && E.is_contiguous() && P.is_contiguous());
+  CHECK_DT(ids, torch::kInt64);
+  const int64_t B = ids.size(0), L = ids.size(1), R = B * L;
+  TORCH_CHECK(E.dim() == 2 && E.size(1) == 64 && P.dim() == 2 && P.size(1) == 64 && P.size(0) >= L,
+              "text_kv_fwd: 64-channel embedding and position tables, at least L positions");
+  TORCH_CHECK(R > 0 && R < (int64_t(1) << 31), "text_kv_fwd: bad row count");
+  TORCH_CHECK(la.size() == 4 && lb.size() == 4, "text_kv_fwd: [lnw, lnb, w, bias] per layer");
+  auto opts = E.options();
+  Tensor x = torch::empty({B, L, 64}, opts);
+  Tensor mean = torch::empty({R}, opts), rstd = torch::empty({R}, opts);
+  Tensor kva = torch::empty({R, 128}, opts.dtype(torch::kBFloat16)), kvb = torch::empty({R, 128}, opts.dtype(torch::kBFloat16));
+  auto proj = [](std::vector<Tensor>& l, Tensor& kv) {
+    TORCH_CHECK(l[0].is_contiguous() && l[0].numel() == 64 && l[1].is_contiguous() && l[1].numel() == 64,
+                "text_kv_fwd: LN affine of 64 channels");
+    TORCH_CHECK(l[2].dim() == 2 && l[2].is_contiguous() && l[2].size(0) == 128 && l[2].size(1) == 64,
+                "text_kv_fwd: w must be (128, 64) contiguous");
+    TORCH_CHECK(l[3].is_contiguous() && l[3].numel() == 128, "text_kv_fwd: bias of 128 columns");
+    return pio::TextKvProj{f32p(l[0]), f32p(l[1]), bfp(l[2]), f32p(l[3]), bfp_mut(kv)};
+  };
+  pio::TextKvFwdArgs a{};
+  a.ids = ids.data_ptr<int64_t>();
+  a.E = f32p(E);
+  a.P = f32p(P);
+  a.scale = (float)scale;
+  a.V = E.size(0);
+  a.L = (int)L;
+  a.R = (int)R;
+  a.eps = (float)eps;
+  a.a = proj(la, kva);
+  a.b = proj(lb, kvb);
+  a.X = x.data_ptr<float>();
+  a.mean = mean.data_ptr<float>();
+  a.rstd = rstd.data_ptr<float>();
+  TORCH_CHECK(pio::text_kv_fwd_launch(a, stream()), "text_kv_fwd: operands must be 16-byte aligned");
+  checked_sync("text_kv_fwd");
+  return {x, mean, rstd, kva, kvb};
+}
+
+// dx (R, 64) = LN_bwd over both layers' dK|dV (ga / gb fp32 (R, 128)); la / lb = [lnw, lnb, w bf16];
+// grads = [dlnw, dlnb, dW, db] of layer a then of layer b: plain / replicated accumulators, or
+// (slab) (ceil(R / 64), ·) views of ONE slab (see vec_target)
+Tensor text_kv_bwd(Tensor ga, Tensor gb, Tensor x, Tensor mean, Tensor rstd, std::vector<Tensor> la,
+                   std::vector<Tensor> lb, std::vector<Tensor> grads, bool slab, OptT job_slab,
+                   std::vector<Tensor> job_dsts, std::vector<int64_t> job_offs) {
+  CHECK_CUDA(ga); CHECK_CUDA(x);
+  const int64_t R = ga.size(0);
+  TORCH_CHECK(ga.dim() == 2 && ga.is_contiguous() && ga.size(1) == 128 && gb.is_contiguous() && gb.dim() == 2 &&
+                  gb.size(0) == R && gb.size(1) == 128,
+              "text_kv_bwd: dK|dV must be (R, 128) contiguous");
+  TORCH_CHECK(x.is_contiguous() && x.numel() == R * 64 && mean.is_contiguous() && mean.numel() == R &&
+                  rstd.is_contiguous() && rstd.numel() == R,
+              "text_kv_bwd: x (R, 64) and its row statistics");
+  TORCH_CHECK(R > 0 && R < kTallRows, "text_kv_bwd: bad row count");
+  TORCH_CHECK(!g_det || slab, "deterministic mode: text_kv_bwd parameter gradients need slab mode");
+  TORCH_CHECK(la.size() == 3 && lb.size() == 3 && grads.size() == 8, "text_kv_bwd: [lnw, lnb, w] per layer, 8 targets");
+  const int64_t sr = slab ? (R + 63) / 64 : 0;
+  int vrs = -1;
+  auto layer = [&](const Tensor& g, std::vector<Tensor>& l, int t0) {
+    TORCH_CHECK(l[0].is_contiguous() && l[0].numel() == 64 && l[1].is_contiguous() && l[1].numel() == 64,
+                "text_kv_bwd: LN affine of 64 channels");
+    TORCH_CHECK(l[2].dim() == 2 && l[2].is_contiguous() && l[2].size(0) == 128 && l[2].size(1) == 64,
+                "text_kv_bwd: w must be (128, 64) contiguous");
+    pio::TextKvGrad o{};
+    o.G = f32p(g);
+    o.lnw = f32p(l[0]);
+    o.lnb = f32p(l[1]);
+    o.W = bfp(l[2]);
+    o.dlnw = vec_target(grads[t0], 64, "dlnw", vrs, sr);
+    o.dlnb = vec_target(grads[t0 + 1], 64, "dlnb", vrs, sr);
+    o.dW = vec_target(grads[t0 + 2], 128 * 64, "dW", vrs, sr);
+    o.db = vec_target(grads[t0 + 3], 128, "db", vrs, sr);
+    return o;
+  };
+  Tensor dx = torch::empty({R, 64}, ga.options());
+  pio::TextKvBwdArgs a{};
+  a.a = layer(ga, la, 0);
+  a.b = layer(gb, lb, 4);
+  a.X = f32p(x);
+  a.mean = f32p(mean);
+  a.rstd = f32p(rstd);
+  a.dX = dx.data_ptr<float>();
+  a.vrs = vrs < 0 ? 0 : vrs;
+  a.slab = slab ? 1 : 0;
+  a.R = (int)R;
+  a.job = make_job(job_slab, job_dsts, job_offs);
+  TORCH_CHECK(pio::text_kv_bwd_launch(a, stream()), "text_kv_bwd: operands must be 16-byte aligned");
+  return dx;
+}
+
 void embed_bwd(Tensor ids, Tensor g, OptT dE, OptT dP, double scale, OptT job_slab, std::vector<Tensor> job_dsts,
                std::vector<int64_t> job_offs) {
   TORCH_CHECK(g.is_contiguous() && ids.is_contiguous());
@@ -2496,6 +2591,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dW"), py::arg("db"), py::arg("pe") = py::none(), py::arg("kin") = -1, py::arg("slab") = false,
         py::arg("job_slab") = py::none(), py::arg("job_dsts") = std::vector<Tensor>(),
         py::arg("job_offs") = std::vector<int64_t>(), py::arg("dx_out") = py::none(), py::arg("pe_index") = py::none());
+  m.def("text_kv_fwd", &text_kv_fwd, py::arg("ids"), py::arg("E"), py::arg("P"), py::arg("scale"), py::arg("eps"),
+        py::arg("la"), py::arg("lb"));
+  m.def("text_kv_bwd", &text_kv_bwd, py::arg("ga"), py::arg("gb"), py::arg("x"), py::arg("mean"), py::arg("rstd"),
+        py::arg("la"), py::arg("lb"), py::arg("grads"), py::arg("slab") = false, py::arg("job_slab") = py::none(),
+        py::arg("job_dsts") = std::vector<Tensor>(), py::arg("job_offs") = std::vector<int64_t>());
   m.def("wgrad", &wgrad, py::arg("g"), py::arg("a"), py::arg("amode"), py::arg("mean"), py::arg("rstd"), py::arg("lnw"),
         py::arg("lnb"), py::arg("rows_per_wg"), py::arg("dW"), py::arg("db"), py::arg("pe") = py::none(),
         py::arg("kin") = -1, py::arg("pe_index") = py::none());

@@ -186,6 +186,42 @@ struct LnLinearBwdArgs {
   PeSplit ps;
   SlabJob job;                  // the previous kernel's slab reduction, in appended workgroups
 };
+// The text encoder's input pass (rowgemm.hip text_kv_fwd / text_kv_bwd): both cross layers'
+// LayerNorm + K|V projection of the embedded token rows, 64 channels → 2·64 columns per layer.
+// one layer's LN affine (fp32), bf16 K|V weight (128, 64), bias (128) and its bf16 (R, 128) output
+struct TextKvProj {
+  const float *lnw, *lnb;
+  const uint16_t* W;
+  const float* bias;
+  uint16_t* KV;
+};
+// x = E[ids]·scale + P[r mod L] (fp32 (R, 64), V table rows), its LN row statistics, both K|V
+struct TextKvFwdArgs {
+  const int64_t* ids;
+  const float *E, *P;
+  float scale;
+  long long V;
+  int L, R;
+  float eps;
+  TextKvProj a, b;
+  float *X, *mean, *rstd;
+};
+// one layer's accumulated dK|dV (fp32 (R, 128)), LN affine, weight and gradient targets
+struct TextKvGrad {
+  const float* G;
+  const float *lnw, *lnb;
+  const uint16_t* W;
+  float *dlnw, *dlnb, *dW, *db;
+};
+// dX = LN_bwd(G_a·W_a∘γ_a + G_b·W_b∘γ_b); the parameter-gradient partials of both layers into
+// replicas or one slab (vrs: the shared replica / slab row stride)
+struct TextKvBwdArgs {
+  TextKvGrad a, b;
+  const float *X, *mean, *rstd;
+  float* dX;
+  int vrs, slab, R;
+  SlabJob job;                  // the previous kernel's slab reduction, in appended workgroups
+};
 // dW (+)= Gᵀ·A', db (+)= Σ rows G; amode: A' = A (0) | LN(A) (1) | GELU(A) (2)
 struct WgradArgs {
   RowsIn G; int N;
@@ -491,6 +527,9 @@ void post_attn_bwd_launch(const PostAttnBwdArgs& a, int C, hipStream_t st);
 bool ln_linear_post_attn_bwd_launch(const LnLinearPostAttnBwdArgs& a, int C, hipStream_t st);
 void ln_linear_bwd_launch(const LnLinearBwdArgs& a, hipStream_t st);
 void wgrad_launch(const WgradArgs& a, hipStream_t st);
+// false (nothing launched) when an operand is not 16-byte aligned
+bool text_kv_fwd_launch(const TextKvFwdArgs& a, hipStream_t st);
+bool text_kv_bwd_launch(const TextKvBwdArgs& a, hipStream_t st);
 unsigned check_errors_rowgemm(bool reset);
 // ---- sample_block.hip ----
 bool sb_fwd_launch(const SBFwdArgs& a, int C, hipStream_t st);

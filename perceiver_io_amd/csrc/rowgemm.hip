@@ -424,6 +424,33 @@ __device__ __forceinline__ void g_store(const float (&v)[2][8], uint16_t* sG, in
 template <int NCH>
 constexpr int ln_linear_fwd_smem() { return 2 * 64 * (32 * NCH + 8) * 2 + 64 * 68 * 4; }
 
+// LayerNorm statistics of this thread's row (row-pass layout; the four lanes of a row agree)
+template <int NCH>
+__device__ __forceinline__ void ln_row_stats(const float (&xv)[NCH][8], int Kin, float eps, float& mean, float& rstd) {
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < NCH; ++j)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) s += xv[j][e];
+  mean = quad_sum(s) / Kin;
+  float q = 0.f;
+#pragma unroll
+  for (int j = 0; j < NCH; ++j)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float d = rp_col(j) + e < Kin ? xv[j][e] - mean : 0.f;
+      // an explicit fused multiply-add: left to the compiler's contraction, some of a row's
+      // squares are formed as packed multiplies and added, and which ones differs from kernel to
+      // kernel — kernels that share these statistics (text_kv_fwd) must agree to the bit
+      q = __builtin_fmaf(d, d, q);
+    }
+  rstd = rsqrtf(quad_sum(q) / Kin + eps);
+}
+// the LN affine of one element, with its one fused multiply-add explicit (see ln_row_stats)
+__device__ __forceinline__ float ln_affine(float x, float mean, float rstd, float g, float b) {
+  return __builtin_fmaf((x - mean) * rstd, g, b);
+}
+
 // the LN + GEMM part of one 64-row tile: xv = this thread's rows (row-pass layout), wb = the
 // prefetched first W chunk, gw/gb = LN affine (read when has_ln); smem ≥ ln_linear_fwd_smem
 // AV: every operand meets the vector-load preconditions (checked on the host) — the loads are
@@ -448,26 +475,13 @@ __device__ __forceinline__ void ln_linear_fwd_tile(float (&xv)[NCH][8], bf16x8 (
   const int wk = w_rs > Kin ? w_rs : Kin;
   const bool yvec = (N & 7) == 0 && (y_rs & 7) == 0 && aligned16(Y);
   if (has_ln) {
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < NCH; ++j)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) s += xv[j][e];
-    const float mean = quad_sum(s) / Kin;
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < NCH; ++j)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float d = rp_col(j) + e < Kin ? xv[j][e] - mean : 0.f;
-        q += d * d;
-      }
-    const float rstd = rsqrtf(quad_sum(q) / Kin + eps);
+    float mean, rstd;
+    ln_row_stats<NCH>(xv, Kin, eps, mean, rstd);
     if ((threadIdx.x & 3) == 0 && gr < R && mean_out && part == nparts - 1) { mean_out[gr] = mean; rstd_out[gr] = rstd; }
 #pragma unroll
     for (int j = 0; j < NCH; ++j)
 #pragma unroll
-      for (int e = 0; e < 8; ++e) xv[j][e] = (xv[j][e] - mean) * rstd * gw[j][e] + gb[j][e];
+      for (int e = 0; e < 8; ++e) xv[j][e] = ln_affine(xv[j][e], mean, rstd, gw[j][e], gb[j][e]);
   }
   lds_row_write_bf16<NCH>(sA, LD, xv);
 
@@ -1079,6 +1093,51 @@ constexpr int ln_linear_bwd_smem() {
   return ln_linear_bwd_loop_smem<NCH>() + 8 * 32 * NCH * 4 + 4 * 64 * 4;
 }
 
+// the chunk loop of the LN-Linear backward for one 64-row tile: acc += G·W over 64-column chunks of
+// N (gv / wb: the prefetched first chunk, the next one fetched during each GEMM), and for the
+// chunks that are this part's, dW += Gᵀ·sXn and db += Σ G.  Ends after a barrier: the LDS tiles
+// are free.
+template <typename TG, int NCH, int MAXT>
+__device__ __forceinline__ void ln_linear_bwd_chunks(float (&gv)[2][8], bf16x8 (&wb)[NCH], f32x16 (&acc)[MAXT],
+                                                     const TG* __restrict__ G, int g_rs, int N,
+                                                     const uint16_t* __restrict__ W, int w_rs, int wk, int Kin, int m0,
+                                                     int R, bool gvec, bool wvec, uint16_t* sG, uint16_t* sW,
+                                                     const uint16_t* sXn, float* sPb, float* __restrict__ dW,
+                                                     float* __restrict__ db, int vrs, int wrs, int slab, int part,
+                                                     int nparts) {
+  constexpr int KP = 32 * NCH, LD = KP + 8, LDG = 64 + 8;
+  const int w = wave_id(), l = lane_id();
+  for (int nc = 0; nc < N; nc += 64) {
+    g_store(gv, sG, LDG);
+    tile_store<NCH>(wb, sW, LD, 64, KP);
+    float cs[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) cs[e] = gv[0][e] + gv[1][e];
+    lds_sync();
+    if (nc + 64 < N) {
+      g_fetch<TG>(gv, G, g_rs, m0, R, nc + 64, N, gvec);
+      tile_fetch<NCH>(wb, W, w_rs, nc + 64, N, 64, wk, KP, wvec);
+    }
+    tile_gemm<MAXT, true, false>(sG, LDG, sW, LD, 64, KP, 64, acc);
+    const bool mine = (nc >> 6) % nparts == part;
+    if (dW && mine) {
+      wgrad_tile<MAXT>(sG, LDG, sXn, LD, 64, KP, N - nc, Kin, rep(dW, wrs, slab) + (long long)nc * Kin, Kin, slab);
+      if (db) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float s = xor32_sum(xor16_sum(cs[e] + dpp<0x128>(cs[e])));  // lanes ≡ l (mod 8)
+          if (l < 8) sPb[w * 64 + 8 * l + e] = s;
+        }
+      }
+    }
+    lds_sync();
+    if (dW && mine && db && threadIdx.x < 64 && nc + (int)threadIdx.x < N) {
+      const int t = threadIdx.x;
+      gadd(rep(db, vrs, slab) + nc + t, sPb[t] + sPb[64 + t] + sPb[128 + t] + sPb[192 + t], slab);
+    }
+  }
+}
+
 // one 64-row tile; dX (incl. dres) is also left in dxo (row-pass registers) for a fused epilogue
 template <typename TG, typename TX, int NCH, bool AV>
 __device__ __forceinline__ void ln_linear_bwd_body(
@@ -1140,35 +1199,8 @@ __device__ __forceinline__ void ln_linear_bwd_body(
   f32x16 acc[MAXT];
 #pragma unroll
   for (int t = 0; t < MAXT; ++t) acc[t] = f32x16{};
-  for (int nc = 0; nc < N; nc += 64) {
-    g_store(gv, sG, LDG);
-    tile_store<NCH>(wb, sW, LD, 64, KP);
-    float cs[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) cs[e] = gv[0][e] + gv[1][e];
-    lds_sync();
-    if (nc + 64 < N) {
-      g_fetch<TG>(gv, G, g_rs, m0, R, nc + 64, N, gvec);
-      tile_fetch<NCH>(wb, W, w_rs, nc + 64, N, 64, wk, KP, wvec);
-    }
-    tile_gemm<MAXT, true, false>(sG, LDG, sW, LD, 64, KP, 64, acc);
-    const bool mine = (nc >> 6) % nparts == part;
-    if (dW && mine) {
-      wgrad_tile<MAXT>(sG, LDG, sXn, LD, 64, KP, N - nc, Kin, rep(dW, wrs, slab) + (long long)nc * Kin, Kin, slab);
-      if (db) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float s = xor32_sum(xor16_sum(cs[e] + dpp<0x128>(cs[e])));  // lanes ≡ l (mod 8)
-          if (l < 8) sPb[w * 64 + 8 * l + e] = s;
-        }
-      }
-    }
-    lds_sync();
-    if (dW && mine && db && threadIdx.x < 64 && nc + (int)threadIdx.x < N) {
-      const int t = threadIdx.x;
-      gadd(rep(db, vrs, slab) + nc + t, sPb[t] + sPb[64 + t] + sPb[128 + t] + sPb[192 + t], slab);
-    }
-  }
+  ln_linear_bwd_chunks<TG, NCH, MAXT>(gv, wb, acc, G, g_rs, N, W, w_rs, wk, Kin, m0, R, gvec, wvec, sG, sW, sXn, sPb, dW,
+                                      db, vrs, wrs, slab, part, nparts);
   for_acc<MAXT>(64, KP, [&](int t, int m, int n, int i) { sF[m * LDF + n] = acc[t][i]; });
   lds_sync();
 
@@ -1375,6 +1407,186 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const TG* __restrict__ G, in
       atomicAdd(rep(db, vrs, 0) + n0 + t, sPb[t] + sPb[64 + t] + sPb[128 + t] + sPb[192 + t]);
     }
   }
+}
+
+// ------------------------------------------------------------------------------------
+// text encoder input (C = 64 channels, 2·64 K|V columns per layer): the encoder's two cross
+// layers (layer_1, layer_n) normalise and project the SAME embedded rows with their own
+// LayerNorm affine and K|V weights, so each direction is one pass over those rows.
+//   text_kv_fwd : x = E[ids]·scale + P[r mod L] (embed_fwd_kernel's arithmetic), one set of
+//                 LayerNorm statistics, then the two LN affine images through ln_linear_fwd_tile:
+//                 x, mean, rstd and both K|V tensors leave in one launch
+//   text_kv_bwd : both layers' dK|dV chunk loops (ln_linear_bwd_chunks: dW, db per layer from its
+//                 own LN(x) image), then ONE LayerNorm backward over dXn₁∘γ₁ + dXnₙ∘γₙ — the LN
+//                 backward is linear in its incoming gradient and x̂ is shared — and dx stored once
+// ------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void text_kv_fwd_kernel(const int64_t* __restrict__ ids, const float* __restrict__ E,
+                                                          const float* __restrict__ P, float scale, long long V, int L,
+                                                          int R, float eps, TextKvProj pa, TextKvProj pb,
+                                                          float* __restrict__ X, float* __restrict__ mean_out,
+                                                          float* __restrict__ rstd_out) {
+  constexpr int NCH = 2, C = 64, N = 128;
+  extern __shared__ __attribute__((aligned(16))) uint16_t smem[];
+  const int m0 = blockIdx.x * 64, gr = m0 + rp_row();
+  // phase 0: the token ids, then both first weight chunks, the LN affines and the table rows
+  long long id = ids[gr < R ? gr : R - 1];
+#if PIO_CHECKS
+  if (id < 0 || id >= V) {
+    pio_flag(kErrEmbedId);
+    id = id < 0 ? 0 : V - 1;
+  }
+#else
+  (void)V;
+#endif
+  bf16x8 wa[NCH], wb[NCH];
+  tile_fetch<NCH>(wa, pa.W, C, 0, N, 64, C, C, true);
+  tile_fetch<NCH>(wb, pb.W, C, 0, N, 64, C, C, true);
+  float ga[NCH][8], ba[NCH][8], gb[NCH][8], bb[NCH][8];
+  row_load<NCH>(ga, pa.lnw, 0, 0, 1, C, true);
+  row_load<NCH>(ba, pa.lnb, 0, 0, 1, C, true);
+  row_load<NCH>(gb, pb.lnw, 0, 0, 1, C, true);
+  row_load<NCH>(bb, pb.lnb, 0, 0, 1, C, true);
+  float xv[NCH][8], pv[NCH][8];
+#pragma unroll
+  for (int j = 0; j < NCH; ++j) {
+    const float* e = E + id * C + rp_col(j);
+    const float* p = P + (long long)((gr < R ? gr : R - 1) % L) * C + rp_col(j);
+    const float4 e0 = *reinterpret_cast<const float4*>(e), e1 = *reinterpret_cast<const float4*>(e + 4);
+    const float4 p0 = *reinterpret_cast<const float4*>(p), p1 = *reinterpret_cast<const float4*>(p + 4);
+    xv[j][0] = e0.x; xv[j][1] = e0.y; xv[j][2] = e0.z; xv[j][3] = e0.w;
+    xv[j][4] = e1.x; xv[j][5] = e1.y; xv[j][6] = e1.z; xv[j][7] = e1.w;
+    pv[j][0] = p0.x; pv[j][1] = p0.y; pv[j][2] = p0.z; pv[j][3] = p0.w;
+    pv[j][4] = p1.x; pv[j][5] = p1.y; pv[j][6] = p1.z; pv[j][7] = p1.w;
+  }
+#pragma unroll
+  for (int j = 0; j < NCH; ++j)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) xv[j][e] = __builtin_fmaf(xv[j][e], scale, pv[j][e]);  // embed_fwd_kernel's e·scale + p
+  row_store<NCH>(xv, X, C, gr, R, C, true);
+  float mean, rstd;
+  ln_row_stats<NCH>(xv, C, eps, mean, rstd);
+  if ((threadIdx.x & 3) == 0 && gr < R) { mean_out[gr] = mean; rstd_out[gr] = rstd; }
+  // the two A-operand images, each through the LN-Linear tile (its LN stage off: done here once)
+  float av[NCH][8];
+#pragma unroll
+  for (int j = 0; j < NCH; ++j)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) av[j][e] = ln_affine(xv[j][e], mean, rstd, ga[j][e], ba[j][e]);
+  ln_linear_fwd_tile<uint16_t, NCH, true>(av, wa, ga, ba, false, m0, R, C, eps, pa.W, C, pa.bias, N, 0, nullptr, 0, pa.KV,
+                                          N, nullptr, nullptr, smem);
+#pragma unroll
+  for (int j = 0; j < NCH; ++j)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) av[j][e] = ln_affine(xv[j][e], mean, rstd, gb[j][e], bb[j][e]);
+  ln_linear_fwd_tile<uint16_t, NCH, true>(av, wb, gb, bb, false, m0, R, C, eps, pb.W, C, pb.bias, N, 0, nullptr, 0, pb.KV,
+                                          N, nullptr, nullptr, smem);
+}
+
+// LDS of text_kv_bwd_kernel: sG | sW | sXa | sXb ([64][72] bf16 each; after the loops the two fp32
+// dXn tiles [64][68] over sG|sW and sXa|sXb), sPart [4][4][64], sPb [4][64]: 41 KB, two
+// workgroups per CU with room to spare
+constexpr int text_kv_bwd_smem() { return 4 * 64 * 72 * 2 + 16 * 64 * 4 + 4 * 64 * 4; }
+
+__global__ __launch_bounds__(256) void text_kv_bwd_kernel(TextKvGrad la, TextKvGrad lb, const float* __restrict__ X,
+                                                          const float* __restrict__ mean,
+                                                          const float* __restrict__ rstd, float* __restrict__ dX, int vrs,
+                                                          int slab, int R, SlabJob job) {
+  constexpr int NCH = 2, C = 64, N = 128, KP = 64, LD = KP + 8, LDG = 64 + 8, LDF = KP + 4;
+  extern __shared__ __attribute__((aligned(16))) uint16_t smem[];
+  if ((int)blockIdx.x >= (R + 63) / 64) {  // appended workgroups: the previous kernel's slab job
+    const int jb = (int)blockIdx.x - (R + 63) / 64;
+    if (jb < job.nblk) slab_reduce_block(job, jb, reinterpret_cast<float4*>(smem));
+    return;
+  }
+  uint16_t* sG = smem;            // [64][LDG]  dK|dV chunk
+  uint16_t* sW = sG + 64 * LDG;   // [64][LD]   W chunk
+  uint16_t* sXa = sW + 64 * LD;   // [64][LD]   LN_a(x)
+  uint16_t* sXb = sXa + 64 * LD;  // [64][LD]   LN_b(x)
+  float* sFa = reinterpret_cast<float*>(sG);   // [64][LDF]  dXn_a, after the loops (over sG | sW)
+  float* sFb = reinterpret_cast<float*>(sXa);  // [64][LDF]  dXn_b (over sXa | sXb)
+  float* sPart = reinterpret_cast<float*>(sXb + 64 * LD);  // [4][4][KP]: dγa, dβa, dγb, dβb per wave
+  float* sPb = sPart + 16 * KP;                            // [4][64]
+  const int m0 = blockIdx.x * 64, gr = m0 + rp_row();
+
+  // ---- phase 0: the rows, their statistics, both LN affines and both layers' first chunks
+  float xv[NCH][8], ga[NCH][8], gb[NCH][8];
+  row_load<NCH>(xv, X, C, gr, R, C, true);
+  const float mu = *(gr < R ? mean + gr : kZero32B);  // address selects: no conditional loads
+  const float rs = *(gr < R ? rstd + gr : kZero32B);
+  row_load<NCH>(ga, la.lnw, 0, 0, 1, C, true);
+  row_load<NCH>(gb, lb.lnw, 0, 0, 1, C, true);
+  float gva[2][8], gvb[2][8];
+  bf16x8 wa[NCH], wb[NCH];
+  g_fetch<float>(gva, la.G, N, m0, R, 0, N, true);
+  tile_fetch<NCH>(wa, la.W, C, 0, N, 64, C, KP, true);
+  g_fetch<float>(gvb, lb.G, N, m0, R, 0, N, true);
+  tile_fetch<NCH>(wb, lb.W, C, 0, N, 64, C, KP, true);
+  {  // each layer's LN(x), its forward GEMM's A operand, for its weight gradient
+    float xn[NCH][8];
+    row_load<NCH>(xn, la.lnb, 0, 0, 1, C, true);
+#pragma unroll
+    for (int j = 0; j < NCH; ++j)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) xn[j][e] += (xv[j][e] - mu) * rs * ga[j][e];
+    lds_row_write_bf16<NCH>(sXa, LD, xn);
+    row_load<NCH>(xn, lb.lnb, 0, 0, 1, C, true);
+#pragma unroll
+    for (int j = 0; j < NCH; ++j)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) xn[j][e] += (xv[j][e] - mu) * rs * gb[j][e];
+    lds_row_write_bf16<NCH>(sXb, LD, xn);
+  }
+
+  // ---- dXn = dK|dV·W per layer (one 32×32 sub-tile per wave), dW and db on the way
+  f32x16 acca[1] = {f32x16{}}, accb[1] = {f32x16{}};
+  ln_linear_bwd_chunks<float, NCH, 1>(gva, wa, acca, la.G, N, N, la.W, C, C, C, m0, R, true, true, sG, sW, sXa, sPb, la.dW,
+                                      la.db, vrs, vrs, slab, 0, 1);
+  ln_linear_bwd_chunks<float, NCH, 1>(gvb, wb, accb, lb.G, N, N, lb.W, C, C, C, m0, R, true, true, sG, sW, sXb, sPb, lb.dW,
+                                      lb.db, vrs, vrs, slab, 0, 1);
+  for_acc<1>(64, KP, [&](int t, int m, int n, int i) {
+    sFa[m * LDF + n] = acca[t][i];
+    sFb[m * LDF + n] = accb[t][i];
+  });
+  lds_sync();
+
+  // ---- row pass: each dXn times its own γ in fp32, summed, one LayerNorm backward
+  float da[NCH][8], db_[NCH][8];
+  lds_row_read<NCH>(da, sFa, LDF);
+  lds_row_read<NCH>(db_, sFb, LDF);
+  float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+  for (int j = 0; j < NCH; ++j)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      xv[j][e] = (xv[j][e] - mu) * rs;  // x̂
+      const float g = da[j][e] * ga[j][e] + db_[j][e] * gb[j][e];
+      ga[j][e] = g;
+      s1 += g;
+      s2 += g * xv[j][e];
+    }
+  s1 = quad_sum(s1) / C;
+  s2 = quad_sum(s2) / C;
+#pragma unroll
+  for (int j = 0; j < NCH; ++j)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) ga[j][e] = rs * (ga[j][e] - s1 - xv[j][e] * s2);  // dX
+  row_store<NCH>(ga, dX, C, gr, R, C, true);
+  colsum_partial<NCH>(da, sPart + 4 * KP, KP);   // dβa
+  colsum_partial<NCH>(db_, sPart + 12 * KP, KP);  // dβb
+#pragma unroll
+  for (int j = 0; j < NCH; ++j)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      da[j][e] *= xv[j][e];
+      db_[j][e] *= xv[j][e];
+    }
+  colsum_partial<NCH>(da, sPart, KP);            // dγa
+  colsum_partial<NCH>(db_, sPart + 8 * KP, KP);  // dγb
+  lds_sync();
+  colsum_flush(sPart, KP, rep(la.dlnw, vrs, slab), C, slab);
+  colsum_flush(sPart + 4 * KP, KP, rep(la.dlnb, vrs, slab), C, slab);
+  colsum_flush(sPart + 8 * KP, KP, rep(lb.dlnw, vrs, slab), C, slab);
+  colsum_flush(sPart + 12 * KP, KP, rep(lb.dlnb, vrs, slab), C, slab);
 }
 
 // ------------------------------------------------------------------------------------
@@ -1622,6 +1834,25 @@ void wgrad_launch(const WgradArgs& a, hipStream_t st) {
   else if (a.G.bf16) wgrad_n<uint16_t, float>(nch, a, rps, st);
   else if (a.A.bf16) wgrad_n<float, uint16_t>(nch, a, rps, st);
   else wgrad_n<float, float>(nch, a, rps, st);
+}
+
+// false (nothing launched) when an operand is not 16-byte aligned: the binding raises
+bool text_kv_fwd_launch(const TextKvFwdArgs& a, hipStream_t st) {
+  if (a.R <= 0 || a.L <= 0 ||
+      !av_ok({a.E, a.P, a.X, a.a.lnw, a.a.lnb, a.a.W, a.a.KV, a.b.lnw, a.b.lnb, a.b.W, a.b.KV}, {}))
+    return false;
+  hipLaunchKernelGGL(text_kv_fwd_kernel, dim3((a.R + 63) / 64), dim3(256), ln_linear_fwd_smem<2>(), st, a.ids, a.E, a.P,
+                     a.scale, a.V, a.L, a.R, a.eps, a.a, a.b, a.X, a.mean, a.rstd);
+  return true;
+}
+
+bool text_kv_bwd_launch(const TextKvBwdArgs& a, hipStream_t st) {
+  if (a.R <= 0 || !av_ok({a.a.G, a.a.lnw, a.a.lnb, a.a.W, a.b.G, a.b.lnw, a.b.lnb, a.b.W, a.X, a.dX}, {})) return false;
+  // + the appended slab-job workgroups
+  const dim3 grid((a.R + 63) / 64 + (a.job.slab ? a.job.nblk : 0));
+  hipLaunchKernelGGL(text_kv_bwd_kernel, grid, dim3(256), text_kv_bwd_smem(), st, a.a, a.b, a.X, a.mean, a.rstd, a.dX,
+                     a.vrs, a.slab, a.R, a.job);
+  return true;
 }
 
 }  // namespace pio

@@ -852,6 +852,42 @@ def embed_fwd(ids, E, P, scale):
     return E[ids] * scale + P[: ids.shape[1]].unsqueeze(0)
 
 
+def text_kv_fwd(ids, E, P, scale, eps, la, lb):
+    """The text encoder's input pass (rowgemm.hip text_kv_fwd_kernel): the embedding, one set of
+    LayerNorm statistics and the K|V projections of layer_1 (la) and layer_n (lb), each
+    [lnw, lnb, w bf16 (128, 64), bias (128)] → (x, mean, rstd, kv_a, kv_b)."""
+    x = embed_fwd(ids, E, P, scale)
+    x2 = x.reshape(-1, x.shape[-1])
+    kva, mean, rstd = ln_linear_fwd(x2, la[0], la[1], eps, la[2], la[3], 0, None, True, True)
+    kvb = ln_linear_fwd(x2, lb[0], lb[1], eps, lb[2], lb[3], 0, None, True, False)[0]
+    return [x, mean, rstd, kva, kvb]
+
+
+def text_kv_bwd(ga, gb, x, mean, rstd, la, lb, grads, slab=False, job_slab=None, job_dsts=(), job_offs=()):
+    """dx of both K|V projections over the shared rows x (rowgemm.hip text_kv_bwd_kernel): each
+    layer's dXn = dK|dV·W times its own γ, summed, then ONE LayerNorm backward; grads =
+    [dlnw, dlnb, dW, db] of layer a then of layer b, accumulated (slab: stored) per layer."""
+    _run_job(job_slab, job_dsts, job_offs)
+    _SLAB[0] = slab
+    try:
+        xf = x.reshape(-1, x.shape[-1]).float()
+        xh = (xf - mean[:, None]) * rstd[:, None]
+        g = None
+        for G, (lnw, lnb, w), (dlnw, dlnb, dW, db) in ((ga, la, grads[0:4]), (gb, lb, grads[4:8])):
+            gf = G.float()
+            dxn = _bf(gf) @ _bf(w.float())
+            _acc(dW, _bf(gf).t() @ _bf(xh * lnw + lnb))
+            _acc(db, gf.sum(0))
+            _acc(dlnw, (dxn * xh).sum(0))
+            _acc(dlnb, dxn.sum(0))
+            g = dxn * lnw if g is None else g + dxn * lnw
+        s1 = g.mean(-1, keepdim=True)
+        s2 = (g * xh).mean(-1, keepdim=True)
+        return rstd[:, None] * (g - s1 - xh * s2)
+    finally:
+        _SLAB[0] = False
+
+
 def embed_bwd(ids, g, dE, dP, scale, job_slab=None, job_dsts=(), job_offs=()):
     _run_job(job_slab, job_dsts, job_offs)
     C = g.shape[-1]

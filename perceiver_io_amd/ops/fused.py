@@ -573,7 +573,8 @@ class _LayerFn(torch.autograd.Function):
                 q, mean_q, rstd_q = K.ln_linear_fwd(xq2, g_q, b_q, EPS, wq, bin_[:C], 0, None, True, True)
             key = id(ps[0])
             ent = src.entries.get(key) if src is not None else None
-            ctx.kv_owner = ent is None
+            # an entry filled in up front (_text_kv_source) is still this layer's to run backward
+            ctx.kv_owner = ent is None or bool(ent.pop("claim", False))
             if ent is None:  # first application of this layer: project K/V (LN over [pixels ‖ PE] if split)
                 kv_sb = False
                 factored = (PE_FACTORED and src is not None and src.pe is not None and src.index is None
@@ -855,6 +856,10 @@ class _LayerFn(torch.autograd.Function):
                                                     flat(bin_, C, 3 * C)])
                 dx_kv = _zero_stand_in(B * M, Ckv, dkv.device)
                 ent["dkv"] = None
+            elif ctx.kv_owner and ent.get("tkv") is not None:
+                # the text input's two projections share one backward (text_kv_bwd): layer_n leaves
+                # its summed dK|dV in its entry, layer_1 — which autograd runs last — launches it
+                dx_kv = _text_kv_backward(K, ent, id(ps[0]), xkv2, mean_kv, rstd_kv, dz2)
             elif ctx.kv_owner:  # the projection's backward, once, over the summed dK/dV
                 if ent.get("pe_D") is not None:
                     dkv2, Rkv = None, B * M
@@ -1549,12 +1554,26 @@ def cross_attention_layer(layer, x_q, x_kv, pad_mask=None):
 # ------------------------------------------------------------------------------------------
 # text embedding
 # ------------------------------------------------------------------------------------------
+# the text encoder's input pass in one launch each way (csrc/rowgemm.hip text_kv_fwd / text_kv_bwd):
+# layer_1 and layer_n normalise and project the same embedded rows, so the embedding, ONE set of
+# LayerNorm statistics and both K|V projections run as one forward kernel, and both projections'
+# backward — one LayerNorm backward over the summed gradient — as one backward kernel.
+# PERCEIVER_TEXT_KV_FUSED=0 restores embed_fwd + one ln_linear_fwd / ln_linear_bwd per layer
+TEXT_KV_FUSED = os.environ.get("PERCEIVER_TEXT_KV_FUSED", "1") != "0"
+TEXT_KV_C = 64  # the kernels' channel count (2·64 K|V columns per layer)
+
+
 class _TextEmbedFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, ids, emb, pos, scale):
+    def forward(ctx, ids, emb, pos, scale, kvp=None):
         K = kernels(emb)
         ids = ids.contiguous()
-        out = K.embed_fwd(ids, emb, pos[: ids.shape[1]].contiguous(), scale)
+        if kvp is not None:  # + both cross layers' LayerNorm and K|V projection (_text_kv_source)
+            C = TEXT_KV_C
+            la, lb = ([ps[2], ps[3], wkv, ps[5][C:]] for ps, wkv in kvp["layers"])
+            out, *kvp["out"] = K.text_kv_fwd(ids, emb, pos[: ids.shape[1]].contiguous(), scale, EPS, la, lb)
+        else:
+            out = K.embed_fwd(ids, emb, pos[: ids.shape[1]].contiguous(), scale)
         ctx.save_for_backward(ids)
         ctx.scale, ctx.emb, ctx.pos = scale, emb, pos
         return out
@@ -1576,14 +1595,88 @@ class _TextEmbedFn(torch.autograd.Function):
                 targets[0].index_put_((ids.reshape(-1),), g.reshape(-1, C) * ctx.scale, accumulate=True)
             if targets[1] is not None:
                 targets[1][: ids.shape[1]] += g.sum(0)
-            return None, None, None, None
+            return None, None, None, None, None
         # scatter-add straight into the (flat-buffer) gradients
         K.embed_bwd(ids, g.contiguous(), targets[0], targets[1], ctx.scale, **_take_job())
-        return None, None, None, None
+        return None, None, None, None, None
 
 
 def text_embed(adapter, ids):
     return _TextEmbedFn.apply(ids, adapter.text_embedding.weight, adapter.pos_encoding, float(adapter.scale))
+
+
+def _text_kv_layers(encoder, ad, ids):
+    """[(ps, wkv)] of layer_1 and layer_n when the fused text input pass applies, else None: a
+    weight-shared layer_n beside layer_1, both cross layers fusable with packed 64 → 2·64 K|V
+    projections, slab weight gradients, no DDP ready point that needs layer_n's gradients before
+    layer_1's backward runs; deterministic mode keeps the per-layer kernels."""
+    from . import deterministic
+
+    C = TEXT_KV_C
+    emb = ad.text_embedding.weight
+    if not (TEXT_KV_FUSED and WGRAD_SLAB) or deterministic() or not hasattr(kernels(emb), "text_kv_fwd"):
+        return None
+    layers = list(encoder.layers())
+    if len(layers) < 2 or any(l[0] is not layers[1][0] for l in layers[2:]) or layers[0][0] is layers[1][0]:
+        return None
+    if (ids.dim() != 2 or ids.dtype != torch.int64 or ids.numel() == 0 or ids.numel() >= TALL_ROWS
+            or emb.shape[1] != C or emb.dtype != torch.float32):
+        return None
+    from ..parallel.reducer import reducer_active
+
+    if reducer_active():  # the "layer_n" ready point fires before layer_1's backward runs
+        return None
+    out = []
+    for cross in (layers[0][0], layers[1][0]):
+        if not _fusable(cross):
+            return None
+        spec, ps = layer_spec_and_params(cross)
+        if not (spec.cross and spec.packed and spec.C == C and ps[2].shape[0] == C):
+            return None
+        out.append((ps, _bf16_weights(spec, ps)[1]))
+    return out
+
+
+def _text_kv_source(ad, ids, layers) -> KVSource:
+    """The text input's KVSource with both cross layers' entries filled in by one launch."""
+    kvp = {"layers": layers}
+    x = _TextEmbedFn.apply(ids, ad.text_embedding.weight, ad.pos_encoding, float(ad.scale), kvp)
+    mean, rstd, kva, kvb = kvp.pop("out")
+    src = KVSource(x)
+    tk = {"first": id(layers[0][0][0]), "layers": layers}
+    for (ps, wkv), kv in zip(layers, (kva, kvb)):
+        # "claim": the layer's first application takes the entry over as its owner (_LayerFn)
+        src.entries[id(ps[0])] = {"kv": kv, "mean": mean, "rstd": rstd, "dkv": None, "factored": False, "wkv": wkv,
+                                  "implicit": None, "sb_bwd": False, "tkv": tk, "claim": True}
+    tk["ents"] = tuple(src.entries[id(ps[0])] for ps, _ in layers)
+    return src
+
+
+def _text_kv_backward(K, ent, key, x2, mean, rstd, like):
+    """The owner backward of a text input projection: layer_n's (autograd runs it first) only
+    leaves its dK|dV in its entry; layer_1's runs both projections' backward in one launch and
+    returns the input gradient for the embedding's backward."""
+    tk = ent["tkv"]
+    if key != tk["first"]:
+        return None
+    ea, eb = tk["ents"]
+    if ea["dkv"] is None or eb["dkv"] is None:
+        raise RuntimeError("fused encoder: the text input backward needs the key/value gradients of both layer_1 "
+                           "and layer_n")
+    C = TEXT_KV_C
+    R = x2.shape[0]
+    sl = _GradSlab(R, [C, C, 2 * C * C, 2 * C] * 2, like)
+    ops, dsts = [], []
+    for ps, wkv in tk["layers"]:
+        ops.append([ps[2].detach(), ps[3].detach(), wkv])
+        flat = [None if _grad_of(p) is None else _grad_of(p).view(-1) for p in (ps[2], ps[3], ps[4], ps[5])]
+        dsts += [flat[0], flat[1], None if flat[2] is None else flat[2][C * C:3 * C * C],
+                 None if flat[3] is None else flat[3][C:3 * C]]
+    dx = K.text_kv_bwd(ea["dkv"].view(R, 2 * C), eb["dkv"].view(R, 2 * C), x2, mean, rstd, ops[0], ops[1],
+                       sl.targets(), slab=True, **_take_job())
+    sl.defer(K, dsts)
+    ea["dkv"] = eb["dkv"] = None
+    return dx
 
 
 # ------------------------------------------------------------------------------------------
@@ -1594,7 +1687,8 @@ def encoder_forward(encoder, x, pad_mask=None):
 
     ad = encoder.input_adapter
     if isinstance(ad, TextInputAdapter):
-        src = KVSource(text_embed(ad, x))
+        kv_layers = _text_kv_layers(encoder, ad, x)
+        src = _text_kv_source(ad, x, kv_layers) if kv_layers is not None else KVSource(text_embed(ad, x))
     elif isinstance(ad, ImageInputAdapter) and not x.requires_grad:
         ad.check_shape(x)
         pix = x.reshape(x.shape[0], -1, ad.num_image_channels).float().contiguous()

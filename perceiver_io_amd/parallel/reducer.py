@@ -71,6 +71,13 @@ def ready_point_armed(module: torch.nn.Module, name: str) -> bool:
     return any(red.armed and red.owns_point(module, name) for red in _ACTIVE)
 
 
+def reducer_active() -> bool:
+    """Whether a gradient reducer is live (overlapped or not).  A caller whose fusion would move
+    gradients of one ready-point range past that point stays on its per-layer path then — with
+    the ready points and without, so the two reducer modes keep computing the same bits."""
+    return bool(_ACTIVE)
+
+
 def bucket_ready_point(x: torch.Tensor, module: torch.nn.Module, name: str) -> torch.Tensor:
     """Mark ``x`` as ready point ``name`` of the armed reducer that planned ``module``."""
     if not _ACTIVE or not torch.is_grad_enabled() or not x.requires_grad:
