@@ -7,6 +7,7 @@
 
 #include "host_api.h"
 
+#include <tuple>
 #include <unordered_map>
 #include <vector>
 
@@ -146,6 +147,34 @@ std::vector<Tensor> attn_fwd(Tensor q, Tensor k, Tensor v, OptT kmask, int64_t H
   }
   pio::attn_fwd_launch(a, (int)D, bfp_mut(O), L.data_ptr<float>(), opp, mlp, (int)std::max<int64_t>(1, nsplit), stream());
   return {O, L};
+}
+
+// head-averaged attention weights of a forward (attn_weights.hip): q (B|1, Nq, >= H·D), k (B, Nk,
+// >= H·D) bf16 views as attn_fwd takes them, lse (B, Nq, H) fp32 as attn_fwd returned it →
+// (avg (B, Nq, Nk) fp32 | None, mass (B, Nk) fp32 | None).  Inference only.
+std::tuple<OptT, OptT> attn_weights(Tensor q, Tensor k, OptT kmask, Tensor lse, int64_t H, int64_t D, double scale,
+                                    bool want_avg, bool want_mass) {
+  TORCH_CHECK(want_avg || want_mass, "attn_weights: at least one of avg / mass must be requested");
+  auto a = make_args(q, k, k, kmask, (int)H, (int)D, scale, 0.0, c10::nullopt, 0);
+  CHECK_CUDA(lse);
+  TORCH_CHECK(lse.is_contiguous() && lse.dim() == 3 && lse.size(0) == a.B && lse.size(1) == a.Nq && lse.size(2) == H,
+              "attn_weights: lse must be (B, Nq, H) contiguous");
+  TORCH_CHECK(a.B <= 65535 && a.Nk <= (1 << 26), "attn_weights: at most 65535 samples and 2^26 keys per call");
+  // the kernel indexes a sample's LSE rows with 32-bit offsets
+  TORCH_CHECK((int64_t)a.Nq * H < (int64_t(1) << 31), "attn_weights: Nq * H must be below 2^31");
+  auto opts = q.options().dtype(torch::kFloat32);
+  const int nchunks = pio::attn_weights_chunks(a.B, a.Nq, a.Nk);
+  OptT avg, mass;
+  Tensor part;
+  if (want_avg) avg = torch::empty({a.B, a.Nq, a.Nk}, opts);
+  if (want_mass) {
+    mass = torch::empty({a.B, a.Nk}, opts);
+    if (nchunks > 1) part = torch::empty({a.B, nchunks, a.Nk}, opts);
+  }
+  pio::attn_weights_launch(a, (int)D, f32p(lse), want_avg ? avg->data_ptr<float>() : nullptr,
+                           want_mass ? mass->data_ptr<float>() : nullptr,
+                           part.defined() ? part.data_ptr<float>() : nullptr, nchunks, stream());
+  return {avg, mass};
 }
 
 // returns (dq, dk, dv) fp32; dq is per batch even when q is batch-broadcast.  Optional
@@ -2549,6 +2578,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("site") = 0, py::arg("dq_zeroed") = false, py::arg("kv_zeroed") = false,
         py::arg("job_slab") = py::none(), py::arg("job_dsts") = std::vector<Tensor>{},
         py::arg("job_offs") = std::vector<int64_t>{});
+  m.def("attn_weights", &attn_weights, py::arg("q"), py::arg("k"), py::arg("kmask"), py::arg("lse"), py::arg("H"),
+        py::arg("D"), py::arg("scale"), py::arg("want_avg"), py::arg("want_mass"));
   m.def("attn_bwd_zero_plan", &pio::attn_bwd_zero_plan, py::arg("B"), py::arg("H"), py::arg("Nq"), py::arg("Nk"),
         py::arg("D"));
   m.def("ln_linear_fwd", &ln_linear_fwd, py::arg("x"), py::arg("lnw"), py::arg("lnb"), py::arg("eps"), py::arg("w"),

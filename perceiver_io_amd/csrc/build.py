@@ -34,6 +34,7 @@ HIP_FLAGS = [f"--offload-arch={ARCH}", "-fPIC", "-std=c++17", "-ffp-contract=fas
 # default (its 160-channel LN-linear backward would spill without the AGPR file)
 _VGPR_FORM = ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]
 PER_FILE_FLAGS = {"chain.hip": _VGPR_FORM, "attention_pe.hip": _VGPR_FORM, "ce_head.hip": _VGPR_FORM,
+                  "attn_weights.hip": _VGPR_FORM,
                   "persist.hip": _VGPR_FORM, "topk_head.hip": _VGPR_FORM,
                   # lamb.hip forms the same update in two kernels and needs it bit-identical in both: no
                   # compiler-chosen contraction (its fused multiply-adds are explicit fmaf calls)

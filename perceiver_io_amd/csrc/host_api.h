@@ -332,6 +332,17 @@ void attn_bwd_pe_launch(const PeBwdArgs& a0, int nkb, int bsplit, hipStream_t st
 int attn_fwd_pe_auto_splits(int B, int H, int ncu);
 // splits × 32-key chunks covering M keys; grid (batch groups, splits, heads), 4 waves each
 void attn_fwd_pe_launch(const PeFwdArgs& a0, hipStream_t st);
+// ---- attn_weights.hip ----
+// query chunks of one launch (its grid.y) for this shape.  One chunk: the kernel stores the mass
+// itself; several: per-chunk partials go to part (B, chunks, Nk) fp32 and a second launch adds them
+// in chunk order.
+int attn_weights_chunks(int B, int Nq, int Nk);
+// head-averaged attention weights of a forward: a (q, k, kmask, B, H, Nq, Nk, scale_log2 read; v and
+// the dropout fields unused), LSE (B, Nq, H) fp32 as attn_fwd wrote it.  avg (B, Nq, Nk) and / or mass
+// (B, Nk) fp32, each may be null (both null: nothing is launched); part: see above, unused when
+// nchunks == 1 or mass is null.  nchunks = attn_weights_chunks(B, Nq, Nk).
+void attn_weights_launch(const AttnArgs& a, int D, const float* LSE, float* avg, float* mass, float* part, int nchunks,
+                         hipStream_t st);
 // ---- augment.hip ----
 void batch_augment_launch(const uint8_t* src, const float* params, float* out, int B, int Hs, int Ws, int C, int oh,
                           int ow, const float* mean, const float* std, hipStream_t st);

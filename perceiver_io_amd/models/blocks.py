@@ -132,18 +132,24 @@ class MultiHeadAttention(nn.Module):
         if ops.get_backend() == "reference":
             # exactly nn.MultiheadAttention(batch_first=True).forward (need_weights=True)
             q, kv = x_q.transpose(0, 1), x_kv.transpose(0, 1)
-            out, _ = F.multi_head_attention_forward(
+            out, w = F.multi_head_attention_forward(
                 q, kv, kv, e, a.num_heads, a.in_proj_weight, a.in_proj_bias, None, None, False,
                 a.dropout, a.out_proj.weight, a.out_proj.bias, training=self.training,
                 key_padding_mask=pad_mask, need_weights=True, attn_mask=attn_mask,
                 use_separate_proj_weight=not a._qkv_same_embed_dim, q_proj_weight=a.q_proj_weight,
                 k_proj_weight=a.k_proj_weight, v_proj_weight=a.v_proj_weight)
+            rec = ops.attention._RECORDER
+            if rec is not None and rec.active:  # the head-averaged weights torch itself returns
+                rec.add(avg=w)
             return out.transpose(0, 1)
         if x_q is x_kv and a._qkv_same_embed_dim:
             q, k, v = F.linear(x_q, a.in_proj_weight, a.in_proj_bias).split(e, dim=-1)
         else:
             q = F.linear(x_q, a.q_weight(), a.in_proj_bias[:e])
             k, v = F.linear(x_kv, a.kv_weight(), a.in_proj_bias[e:]).split(e, dim=-1)
+        rec = ops.attention._RECORDER
+        if rec is not None and rec.active:
+            rec.add(*ops.attention._weights(q, k, a.num_heads, pad_mask, rec.want_avg, not rec.want_avg, attn_mask))
         o = ops.attention.mha_core(q, k, v, a.num_heads, key_padding_mask=pad_mask, attn_mask=attn_mask,
                                    dropout_p=a.dropout if self.training else 0.0)
         return F.linear(o, a.out_proj.weight, a.out_proj.bias)

@@ -190,6 +190,41 @@ class LArPerceiver(torch.nn.Module):
         seg = self.segment_sparse(values, index, kmask, labels=qlab)
         return seg._replace(count=count)
 
+    @torch.no_grad()
+    def attention_map(self, img, capacity: Optional[int] = None, bucket: int = 2048, layer: int = 0) -> torch.Tensor:
+        """``(B, H·W)`` fp32: the attention mass each pixel receives in the encoder's cross-attention
+        application ``layer`` (0 = ``layer_1``, then ``layer_n``'s applications), 0 at unlit pixels.
+
+        The event is compacted as in :meth:`segment` (same ``capacity`` rules, the same single host
+        read when ``capacity=None``), only the lit pixels are encoded under
+        ``ops.record_attention``, and the mass of the chosen application is scattered to the pixel
+        positions.  A sample's map sums to the latent count (0 for an event without lit pixels);
+        pixels past the capacity stay 0.  The decoder does not run.
+
+        Eager backends only: the encoder runs through its layer modules in fp32, where the weights
+        come from the materialised per-head softmax of the lit keys (``B × H × latents × capacity``
+        floats), not from the ``attn_weights`` kernel.  The fused encoder executor is not recorded
+        (``ops.record_attention``); with it selected this method raises before doing any work."""
+        from .. import ops
+        from ..data.lartpc import _round_up
+
+        enc = self.perceiver.encoder
+        if ops.use_hip(enc.latent):  # before any work: the refusal costs nothing
+            raise RuntimeError("attention_map: the fused encoder is not recorded; run under ops.backend('torch')")
+        b = img.shape[0]
+        flat = img.reshape(b, -1).float().contiguous()
+        kern = ops.emulation  # the eager backend's compaction (use_hip is false here)
+        if capacity is None:
+            count = kern.nonzero_compact(flat, 0)[3]
+            capacity = _round_up(int(count.max()), bucket)
+        values, index, kmask, _ = kern.nonzero_compact(flat, int(capacity))
+        with ops.record_attention(enc, "mass") as rec:
+            enc.forward_inputs(sparse_inputs(enc.input_adapter, values, index), kmask)
+        if not 0 <= layer < len(rec.entries):
+            raise ValueError(f"attention_map: layer must be in [0, {len(rec.entries)}), got {layer}")
+        mass = rec.entries[layer]["tensor"]  # (B, capacity), exactly 0 on the padding slots
+        return torch.zeros_like(flat).scatter_add_(1, index, mass.to(flat.dtype))
+
 
 def iou(confusion: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """``(per-class IoU (K,), mean IoU)`` of a confusion matrix (rows = label, columns =

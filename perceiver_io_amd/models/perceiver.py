@@ -76,6 +76,24 @@ class PerceiverEncoder(nn.Module):
             return ops.fused.encoder_forward(self, x, pad_mask), pad_mask
         return self.forward_inputs(self.input_adapter(x), pad_mask, attn_mask), pad_mask
 
+    @torch.no_grad()
+    def input_attention(self, x, pad_mask=None):
+        """Which inputs the latents read: for each cross-attention application in order (``layer_1``,
+        then ``layer_n`` ``num_layers − 1`` times) the ``(B, M)`` fp32 attention mass of the M inputs —
+        the head-averaged pre-dropout weights summed over the latents (``ops.record_attention``).
+        Over the unpadded inputs of a sample it sums to the latent count; padded inputs get exactly
+        0.  Call under ``eval()``.
+
+        Eager backends only: the encoder runs through its layer modules, where the weights come from
+        the materialised per-head softmax (``B × H × N × M`` floats per layer), not from the
+        ``attn_weights`` kernel.  The fused encoder executor is not recorded
+        (``ops.record_attention``); with it selected this method raises before doing any work."""
+        if ops.use_hip(self.latent):
+            raise RuntimeError("input_attention: the fused encoder is not recorded; run under ops.backend('torch')")
+        with ops.record_attention(self, "mass") as rec:
+            self(x, pad_mask)
+        return [e["tensor"] for e in rec.entries]
+
     def forward_inputs(self, x_in, pad_mask=None, attn_mask=None):
         """Latents for already adapted inputs ``x_in`` (B, M, Kin), bypassing the input adapter
         (used for sparse image inputs: the adapter's rows gathered at the non-zero pixels)."""
@@ -306,6 +324,12 @@ class PerceiverMLM(nn.Module):
         lin = self.decoder.output_adapter.linear
         values, indices, lse = ops.mlm_head.vocab_topk(h, lin.weight, lin.bias, k, idx=real)
         return where, values, indices, lse
+
+    def token_attention(self, x_input, pad_mask=None):
+        """``(B, L)`` fp32: the attention mass each token receives in the encoder's first
+        cross-attention (``PerceiverEncoder.input_attention``, eager backends only), exactly 0 at
+        padded tokens.  No masking is applied; call under ``eval()``."""
+        return self.encoder.input_attention(x_input, pad_mask)[0]
 
     def loss(self, x_input, pad_mask=None, labels=None, x_masked=None):
         """Masked-token cross-entropy (mean over selected positions) without

@@ -230,3 +230,4 @@ def event_compact(img: torch.Tensor, lab: torch.Tensor, words: torch.Tensor, key
 
 
 from . import attention, fused, masking, mlm_head, optim  # noqa: E402,F401
+from .attention import attention_mass, attention_weights, record_attention  # noqa: E402,F401

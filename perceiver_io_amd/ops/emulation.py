@@ -343,6 +343,29 @@ def attn_fwd(q, k, v, kmask, H, D, scale, dropout_p, seed, nsplit, site=0):
     return o, lse2.permute(0, 2, 1).contiguous()
 
 
+def attn_weights(q, k, kmask, lse, H, D, scale, want_avg, want_mass):
+    """Head-averaged attention weights ``(avg (B, Nq, Nk) | None, mass (B, Nk) | None)`` in fp32:
+    ``avg = (1/H) Σ_h P``, ``mass = Σ_n avg``.  With ``lse`` ((B, Nq, H), log2 units, as ``attn_fwd``
+    returns it) ``P = 2^(s·log2e − lse)`` (0 where the LSE is not finite), else the fp32 softmax of the
+    scores; a padded key gives exactly 0, so a row whose keys are all padded is all zeros."""
+    if not (want_avg or want_mass):
+        raise ValueError("attn_weights: at least one of avg / mass must be requested")
+    B, qf, kf, _ = _qkv(q, k, k, H, D)
+    s = torch.matmul(qf, kf.transpose(-1, -2)) * scale  # (B, H, Nq, Nk)
+    if lse is not None:
+        l2 = lse.float().permute(0, 2, 1).unsqueeze(-1)
+        l2 = torch.where(torch.isfinite(l2), l2, torch.full_like(l2, float("inf")))
+        p = torch.exp2(s * LOG2E - l2)
+        if kmask is not None:
+            p = p.masked_fill(kmask.view(B, 1, 1, -1).bool(), 0.0)
+    else:
+        if kmask is not None:
+            s = s.masked_fill(kmask.view(B, 1, 1, -1).bool(), float("-inf"))
+        p = torch.nan_to_num(torch.softmax(s, -1), nan=0.0)
+    avg = p.sum(1) * (1.0 / H)
+    return (avg if want_avg else None), (avg.sum(1) if want_mass else None)
+
+
 def attn_bwd(q, k, v, kmask, o, dO, lse, delta_in, H, D, scale, dropout_p, seed, dq_out, dk_out, dv_out,
              kv_accumulate=False, site=0, dq_zeroed=False, kv_zeroed=False, job_slab=None, job_dsts=(), job_offs=()):
     _run_job(job_slab, job_dsts, job_offs)
