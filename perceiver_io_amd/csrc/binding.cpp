@@ -27,7 +27,8 @@ hipStream_t stream() { return at::hip::getCurrentHIPStream(); }
 // dihedral code outside 0-7); reset clears them
 int64_t check_errors(bool reset) {
   return (int64_t)(pio::check_errors_elementwise(reset) | pio::check_errors_optim(reset) |
-                   pio::check_errors_mlm_head(reset) | pio::check_errors_ce_head(reset) | pio::check_errors_topk_head(reset) |
+                   pio::check_errors_mlm_head(reset) | pio::check_errors_mlm_select(reset) |
+                   pio::check_errors_ce_head(reset) | pio::check_errors_topk_head(reset) |
                    pio::check_errors_rowgemm(reset) | pio::check_errors_pixel_head(reset) |
                    pio::check_errors_soft_ce_head(reset) | pio::check_errors_augment(reset) |
                    pio::check_errors_randaugment(reset) | pio::check_errors_health(reset) |
@@ -1286,65 +1287,42 @@ std::vector<Tensor> ce_fwd(Tensor h, OptT idx, Tensor labels, Tensor w, Tensor b
   CHECK_DT(labels, torch::kInt64);
   CHECK_DT(h, torch::kFloat32);
   CHECK_DT(count, torch::kFloat32);
-  const int M = (int)labels.numel(), C = (int)h.size(1), V = (int)w.size(0);
+  pio::CeFwdArgs a{};
+  const int M = a.M = (int)labels.numel(), C = a.C = (int)h.size(1);
+  a.V = (int)w.size(0);
   TORCH_CHECK(w.size(1) == C && (C == 32 || C == 64 || C == 128), "bad vocab head shape");
   TORCH_CHECK(idx.has_value() || h.size(0) == M, "ce_fwd: h must have one row per label without idx");
-  const int64_t* ip = opt_idx(idx, M);
-  auto f32 = h.options().dtype(torch::kFloat32);
-  if (C == 64) {
-    // two-pass head (ce_head.hip): the forward also forms the per-split Σ_v p·W partials of each
-    // row (the hidden-state gradient up to the row-loss scale once merged); returned with the
-    // splits' (max, sum) as a 4th and 5th output for ce_bwd, which merges them
-    const int ns = pio::ce2_num_splits(M, V);
-    Tensor pml = torch::empty({ns, M, 2}, f32), pacc = torch::empty({ns, M, C}, f32);
-    Tensor picked = torch::empty({M}, f32), lse = torch::empty({M}, f32), loss = torch::empty({}, f32);
-    const int nrb = pio::ce2_row_blocks(M);
-    TORCH_CHECK(nrb <= kCeRowBlockTickets, "ce_fwd: too many rows for the row-block tickets");
-    Tensor blk = torch::empty({2 * nrb}, f32);
-    Tensor hs = torch::empty({M, C}, h.options().dtype(torch::kBFloat16));
-    TORCH_CHECK(count.numel() >= 1 && count.is_contiguous(), "ce_fwd: count must hold one fp32 value");
-    float* zp = nullptr;
-    int64_t zn = 0;
-    if (zero_out.has_value()) {
-      CHECK_DT(*zero_out, torch::kFloat32);
-      TORCH_CHECK(zero_out->is_contiguous() && zero_out->numel() % 4 == 0 && zero_out->get_device() == h.get_device() &&
-                      reinterpret_cast<uintptr_t>(zero_out->data_ptr()) % 16 == 0,
-                  "ce_fwd: zero_out must be a contiguous, 16-byte aligned fp32 buffer of 4k elements");
-      zp = zero_out->data_ptr<float>();
-      zn = zero_out->numel();
-    }
-    Tensor& tk = ce_ticket(h);
-    Tensor& rbt = ce_rb_tickets(h);
-    pio::ce2_fwd_launch(h.data_ptr<float>(), ip, labels.data_ptr<int64_t>(), bfp(w), f32p(bias), M, V, ns,
-                        reinterpret_cast<float2*>(pml.data_ptr<float>()), pacc.data_ptr<float>(), picked.data_ptr<float>(),
-                        bfp_mut(hs), lse.data_ptr<float>(), count.data_ptr<float>(), count_labels ? 1 : 0,
-                        loss.data_ptr<float>(), blk.data_ptr<float>(), reinterpret_cast<unsigned*>(rbt.data_ptr<int>()),
-                        reinterpret_cast<unsigned*>(tk.data_ptr<int>()), zp, zn, stream());
-    checked_sync("ce_fwd");
-    return {loss, lse, hs, pacc, pml};
-  }
-  const int ns = pio::ce_num_splits(M, V);
-  Tensor part = torch::empty({ns, M, 2}, f32), picked = torch::empty({M}, f32);
-  Tensor lse = torch::empty({M}, f32), loss = torch::empty({}, f32);
-  Tensor blk = torch::empty({2 * pio::ce_combine_blocks(M)}, f32);
+  a.hidx = opt_idx(idx, M);
+  // C = 64, the two-pass head (ce_head.hip): the forward also forms the per-split Σ_v p·W partials
+  // of each row (the hidden-state gradient up to the row-loss scale once merged); returned with
+  // the splits' (max, sum) as a 4th and 5th output for ce_bwd, which merges them
+  const pio::CeFwdPlan pl = pio::ce_fwd_plan(C, M, a.V);
+  TORCH_CHECK(pl.rb_tickets <= kCeRowBlockTickets, "ce_fwd: too many rows for the row-block tickets");
   TORCH_CHECK(count.numel() >= 1 && count.is_contiguous(), "ce_fwd: count must hold one fp32 value");
-  Tensor hs = torch::empty({M, C}, h.options().dtype(torch::kBFloat16));
-  Tensor& tk = ce_ticket(h);
-  float* zp = nullptr;
-  int64_t zn = 0;
   if (zero_out.has_value()) {
     CHECK_DT(*zero_out, torch::kFloat32);
     TORCH_CHECK(zero_out->is_contiguous() && zero_out->numel() % 4 == 0 && zero_out->get_device() == h.get_device() &&
                     reinterpret_cast<uintptr_t>(zero_out->data_ptr()) % 16 == 0,
                 "ce_fwd: zero_out must be a contiguous, 16-byte aligned fp32 buffer of 4k elements");
-    zp = zero_out->data_ptr<float>();
-    zn = zero_out->numel();
+    a.zero_out = zero_out->data_ptr<float>();
+    a.zero_n = zero_out->numel();
   }
-  pio::ce_fwd_launch(C, h.data_ptr<float>(), ip, labels.data_ptr<int64_t>(), bfp(w), f32p(bias), M, V,
-                     part.data_ptr<float>(), picked.data_ptr<float>(), lse.data_ptr<float>(), count.data_ptr<float>(),
-                     loss.data_ptr<float>(), blk.data_ptr<float>(), reinterpret_cast<unsigned*>(tk.data_ptr<int>()),
-                     bfp_mut(hs), ns, zp, zn, count_labels ? 1 : 0, stream());
+  auto f32 = h.options().dtype(torch::kFloat32);
+  Tensor pml = torch::empty({pl.nsplit, M, 2}, f32), pacc;
+  if (pl.acc) pacc = torch::empty({pl.nsplit, M, C}, f32);
+  Tensor picked = torch::empty({M}, f32), lse = torch::empty({M}, f32), loss = torch::empty({}, f32);
+  Tensor blk = torch::empty({2 * pl.nblk}, f32);
+  Tensor hs = torch::empty({M, C}, h.options().dtype(torch::kBFloat16));
+  a.H = h.data_ptr<float>(); a.labels = labels.data_ptr<int64_t>(); a.W = bfp(w); a.bias = f32p(bias);
+  a.loss = loss.data_ptr<float>(); a.lse = lse.data_ptr<float>(); a.hs = bfp_mut(hs);
+  a.count = count.data_ptr<float>(); a.count_labels = count_labels ? 1 : 0;
+  a.nsplit = pl.nsplit; a.part_ml = pml.data_ptr<float>(); a.part_acc = pl.acc ? pacc.data_ptr<float>() : nullptr;
+  a.picked = picked.data_ptr<float>(); a.blk = blk.data_ptr<float>();
+  a.ticket = reinterpret_cast<unsigned*>(ce_ticket(h).data_ptr<int>());
+  a.rb_tickets = pl.rb_tickets ? reinterpret_cast<unsigned*>(ce_rb_tickets(h).data_ptr<int>()) : nullptr;
+  pio::ce_fwd_launch(a, stream());
   checked_sync("ce_fwd");
+  if (pl.acc) return {loss, lse, hs, pacc, pml};
   return {loss, lse, hs};
 }
 
@@ -1371,7 +1349,9 @@ OptT ce_bwd(Tensor h, Tensor labels, Tensor w, Tensor bias, Tensor lse, Tensor g
   } else {
     TORCH_CHECK(dH.size(0) == M, "dH must be (M, C) without a rowmap");
   }
-  Tensor sl;
+  TORCH_CHECK(C != 64 || (u.has_value() && u_ml.has_value()),
+              "ce_bwd: the two-pass head (C = 64) needs u and u_ml, the split partials ce_fwd returns with it");
+  pio::CeBwdArgs a{};
   if (u.has_value()) {  // the two-pass head's backward: dW / db pass + the dH rows g·u
     // u: the forward's per-split Σ p·W partials (splits, M, 64), u_ml: their (max, sum) (splits, M, 2)
     CHECK_DT(*u, torch::kFloat32);
@@ -1381,19 +1361,18 @@ OptT ce_bwd(Tensor h, Tensor labels, Tensor w, Tensor bias, Tensor lse, Tensor g
                     u_ml->is_contiguous() && u_ml->dim() == 3 && u_ml->size(0) == u->size(0) && u_ml->size(1) == M &&
                     u_ml->size(2) == 2 && u->size(0) <= 16,
                 "ce_bwd: u must be (splits, M, 64) and u_ml (splits, M, 2) fp32");
-    if (slab) sl = torch::empty({pio::ce2_bwd_splits(M, V), (int64_t)V * C + ((V + 3) & ~3)}, dW.options());
-    pio::ce2_bwd_launch(bfp(h), labels.data_ptr<int64_t>(), bfp(w), f32p(bias), f32p(lse), u->data_ptr<float>(),
-                        reinterpret_cast<const float2*>(u_ml->data_ptr<float>()), (int)u->size(0), f32p(gout),
-                        f32p(count), M, V, dW.data_ptr<float>(), db.data_ptr<float>(),
-                        slab ? sl.data_ptr<float>() : nullptr, accumulate ? 1 : 0, dH.data_ptr<float>(), dH.size(0), rm,
-                        stream());
-    if (slab) return sl;
-    return c10::nullopt;
+    a.part_acc = u->data_ptr<float>(); a.part_ml = u_ml->data_ptr<float>(); a.nsplit = (int)u->size(0);
   }
-  if (slab) sl = torch::empty({pio::ce_dw_splits(M, V), (int64_t)V * C + ((V + 3) & ~3)}, dW.options());
-  pio::ce_bwd_launch(C, bfp(h), labels.data_ptr<int64_t>(), bfp(w), f32p(bias), f32p(lse), f32p(gout),
-                     f32p(count), M, V, dH.data_ptr<float>(), dH.size(0), rm, dW.data_ptr<float>(), db.data_ptr<float>(),
-                     accumulate ? 1 : 0, slab ? sl.data_ptr<float>() : nullptr, g_det ? 1 : 0, stream());
+  Tensor sl;
+  if (slab) sl = torch::empty({pio::ce_bwd_slab_rows(C, M, V), (int64_t)V * C + ((V + 3) & ~3)}, dW.options());
+  a.C = C; a.M = M; a.V = V;
+  a.hs = bfp(h); a.labels = labels.data_ptr<int64_t>(); a.W = bfp(w); a.bias = f32p(bias);
+  a.lse = f32p(lse); a.gout = f32p(gout); a.count = f32p(count);
+  a.dH = dH.data_ptr<float>(); a.dh_rows = dH.size(0); a.rowmap = rm;
+  a.dW = dW.data_ptr<float>(); a.db = db.data_ptr<float>(); a.accumulate = accumulate ? 1 : 0;
+  a.slab = slab ? sl.data_ptr<float>() : nullptr;
+  a.det = g_det ? 1 : 0;
+  pio::ce_bwd_launch(a, stream());
   if (slab) return sl;
   return c10::nullopt;
 }
@@ -1428,9 +1407,12 @@ std::vector<Tensor> vocab_topk(Tensor h, OptT idx, Tensor w, Tensor bias, int64_
   const int ns = pio::vocab_topk_splits(M, V), kt = pio::vocab_topk_kt((int)k);
   Tensor cv = torch::empty({ns, M, kt}, f32), ci = torch::empty({ns, M, kt}, f32.dtype(torch::kInt32));
   Tensor pml = torch::empty({ns, M, 2}, f32);
-  pio::vocab_topk_launch(C, h.data_ptr<float>(), ip, h.size(0), bfp(w), f32p(bias), M, V, (int)k, ns, cv.data_ptr<float>(),
-                         ci.data_ptr<int>(), reinterpret_cast<float2*>(pml.data_ptr<float>()), values.data_ptr<float>(),
-                         indices.data_ptr<int64_t>(), lse.data_ptr<float>(), stream());
+  pio::VocabTopkArgs a{};
+  a.C = C; a.M = M; a.V = V; a.k = (int)k;
+  a.H = h.data_ptr<float>(); a.hidx = ip; a.R = h.size(0); a.W = bfp(w); a.bias = f32p(bias);
+  a.nsplit = ns; a.cand_v = cv.data_ptr<float>(); a.cand_i = ci.data_ptr<int>(); a.part_ml = pml.data_ptr<float>();
+  a.values = values.data_ptr<float>(); a.indices = indices.data_ptr<int64_t>(); a.lse = lse.data_ptr<float>();
+  pio::vocab_topk_launch(a, stream());
   checked_sync("vocab_topk");
   return {values, indices, lse};
 }
@@ -1439,8 +1421,8 @@ std::vector<Tensor> vocab_topk(Tensor h, OptT idx, Tensor w, Tensor bias, int64_
 // row, label smoothing eps.  → {loss (mean over the rows whose label_a is not -100), lse (M,),
 // pred (M,) int32 argmax of the logits (lower class on a tie), the compact bf16 rows, count (1,)}.
 // C ∈ {64, 128}, 1 ≤ V ≤ 1024.
-void soft_ce_check(const Tensor& la, const Tensor& lb, const Tensor& lam, const Tensor& w, const Tensor& bias, int M,
-                   int C, double eps) {
+pio::SoftCeArgs soft_ce_check(const Tensor& la, const Tensor& lb, const Tensor& lam, const Tensor& w, const Tensor& bias,
+                              int M, int C, double eps) {
   CHECK_DT(la, torch::kInt64); CHECK_DT(lb, torch::kInt64); CHECK_DT(lam, torch::kFloat32);
   TORCH_CHECK(la.is_contiguous() && lb.is_contiguous() && lam.is_contiguous() && w.is_contiguous() &&
               bias.is_contiguous(), "soft_ce: operands must be contiguous");
@@ -1450,22 +1432,27 @@ void soft_ce_check(const Tensor& la, const Tensor& lb, const Tensor& lam, const 
               "soft_ce: supported head shapes are C in {64, 128}, 1 <= V <= 1024");
   TORCH_CHECK(M >= 1 && eps >= 0.0 && eps < 1.0, "soft_ce: needs M >= 1 and eps in [0, 1)");
   for (const Tensor* t : {&la, &lb, &lam, &w, &bias}) CHECK_CUDA(*t);
+  pio::SoftCeArgs a{};
+  a.C = C; a.M = M; a.V = (int)V;
+  a.W = bfp(w); a.bias = f32p(bias);
+  a.la = la.data_ptr<int64_t>(); a.lb = lb.data_ptr<int64_t>(); a.lam = f32p(lam); a.eps = (float)eps;
+  return a;
 }
 
 std::vector<Tensor> soft_ce_fwd(Tensor h, Tensor la, Tensor lb, Tensor lam, Tensor w, Tensor bias, double eps) {
   CHECK_CUDA(h);
   CHECK_DT(h, torch::kFloat32);
   TORCH_CHECK(h.dim() == 2 && h.is_contiguous() && h.size(0) < (1 << 24), "soft_ce_fwd: h must be (M, C) contiguous");
-  const int M = (int)h.size(0), C = (int)h.size(1), V = (int)w.size(0);
-  soft_ce_check(la, lb, lam, w, bias, M, C, eps);
+  const int M = (int)h.size(0), C = (int)h.size(1);
+  pio::SoftCeArgs a = soft_ce_check(la, lb, lam, w, bias, M, C, eps);
   auto f32 = h.options().dtype(torch::kFloat32);
   const int nrt = pio::soft_ce_row_tiles(M);
   Tensor loss = torch::empty({}, f32), lse = torch::empty({M}, f32), count = torch::empty({1}, f32);
   Tensor pred = torch::empty({M}, f32.dtype(torch::kInt32)), hs = torch::empty({M, C}, f32.dtype(torch::kBFloat16));
   Tensor blk = torch::empty({2 * nrt}, f32);
-  pio::soft_ce_fwd_launch(C, h.data_ptr<float>(), bfp(w), f32p(bias), la.data_ptr<int64_t>(), lb.data_ptr<int64_t>(),
-                          f32p(lam), (float)eps, M, V, lse.data_ptr<float>(), pred.data_ptr<int>(), bfp_mut(hs),
-                          blk.data_ptr<float>(), loss.data_ptr<float>(), count.data_ptr<float>(), stream());
+  a.H = h.data_ptr<float>(); a.hs = bfp_mut(hs); a.lse = lse.data_ptr<float>(); a.count = count.data_ptr<float>();
+  a.pred = pred.data_ptr<int>(); a.blk = blk.data_ptr<float>(); a.loss = loss.data_ptr<float>();
+  pio::soft_ce_fwd_launch(a, stream());
   checked_sync("soft_ce_fwd");
   return {loss, lse, pred, hs, count};
 }
@@ -1477,7 +1464,7 @@ void soft_ce_bwd(Tensor hs, Tensor la, Tensor lb, Tensor lam, Tensor w, Tensor b
   CHECK_CUDA(hs);
   TORCH_CHECK(hs.dim() == 2 && hs.is_contiguous(), "soft_ce_bwd: hs must be the compact (M, C) bf16 rows");
   const int M = (int)hs.size(0), C = (int)hs.size(1), V = (int)w.size(0);
-  soft_ce_check(la, lb, lam, w, bias, M, C, eps);
+  pio::SoftCeArgs a = soft_ce_check(la, lb, lam, w, bias, M, C, eps);
   for (const Tensor* t : {&lse, &gout, &count, &dH, &dW, &db}) {
     CHECK_CUDA(*t); CHECK_DT(*t, torch::kFloat32);
     TORCH_CHECK(t->is_contiguous(), "soft_ce_bwd: operands must be contiguous");
@@ -1485,9 +1472,10 @@ void soft_ce_bwd(Tensor hs, Tensor la, Tensor lb, Tensor lam, Tensor w, Tensor b
   TORCH_CHECK(lse.numel() == M && gout.numel() >= 1 && count.numel() >= 1, "soft_ce_bwd: bad lse / gout / count");
   TORCH_CHECK(dH.numel() == (int64_t)M * C && dW.numel() == (int64_t)V * C && db.numel() == V,
               "soft_ce_bwd: dH (M, C), dW (V, C), db (V,)");
-  pio::soft_ce_bwd_launch(C, bfp(hs), bfp(w), f32p(bias), la.data_ptr<int64_t>(), lb.data_ptr<int64_t>(), f32p(lam),
-                          (float)eps, f32p(lse), f32p(gout), f32p(count), M, V, dH.data_ptr<float>(),
-                          dW.data_ptr<float>(), db.data_ptr<float>(), accumulate ? 1 : 0, stream());
+  a.hs = bfp_mut(hs); a.lse = lse.data_ptr<float>(); a.count = count.data_ptr<float>();  // read only here
+  a.gout = f32p(gout); a.dH = dH.data_ptr<float>(); a.dW = dW.data_ptr<float>(); a.db = db.data_ptr<float>();
+  a.accumulate = accumulate ? 1 : 0;
+  pio::soft_ce_bwd_launch(a, stream());
 }
 
 // MixUp / CutMix of a channels-last batch with its flipped self; mix = {mode, lambda, y0, y1, x0, x1}

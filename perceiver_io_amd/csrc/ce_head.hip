@@ -42,6 +42,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "head_common.h"
 
 namespace pio {
 
@@ -52,11 +53,9 @@ constexpr int RB = 128;          // pass 1: rows per workgroup (4 waves × 32)
 constexpr int VC = 64;           // pass 1: vocab entries per staged chunk
 constexpr int VB2 = 128;         // pass 2: vocab entries per workgroup (4 waves × 32)
 constexpr int HT = 64;           // pass 2: rows per staged H tile
-constexpr float kL2E = 1.4426950408889634f;
-constexpr float kLN2 = 0.6931471805599453f;
 constexpr float kRescale = 8.f;  // lazy-rescale threshold (log2 units)
 constexpr float kRescaleSum = 256.f;  // 2^kRescale: a tile's Σ p above it takes the rescale branch
-constexpr int kCeMaxSplitsFwd = 16;  // ce2_num_splits caps the vocab splits of pass 1 here
+constexpr int kCeMaxSplitsFwd = 16;  // ce2_fwd_plan caps the vocab splits of pass 1 here
 // pass 2 at a vocabulary this small (a classifier head: most tile rows' labels fall inside every
 // wave's 32 vocab entries) takes the one-hot term inside the tile, d = p − [label = v] (one
 // compare per logit), instead of the per-hit ballot scan, which would serialise on every row
@@ -135,19 +134,7 @@ __global__ __launch_bounds__(256) void ce2_fwd_kernel(const float* __restrict__ 
   bf16x8 hb[4];
   {
     const long long src = hidx ? hidx[rin ? gr : 0] : (long long)(rin ? gr : 0);
-    const float* hp = Hm + src * C + 8 * hh;
-    float4 a[4], b[4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      a[s] = *reinterpret_cast<const float4*>(rin ? hp + 16 * s : kZero32B);
-      b[s] = *reinterpret_cast<const float4*>(rin ? hp + 16 * s + 4 : kZero32B);
-    }
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      hb[s][0] = (short)f2bf(a[s].x); hb[s][1] = (short)f2bf(a[s].y); hb[s][2] = (short)f2bf(a[s].z);
-      hb[s][3] = (short)f2bf(a[s].w); hb[s][4] = (short)f2bf(b[s].x); hb[s][5] = (short)f2bf(b[s].y);
-      hb[s][6] = (short)f2bf(b[s].z); hb[s][7] = (short)f2bf(b[s].w);
-    }
+    load_row_operand(hb, Hm + src * C + 8 * hh, rin);
     if (split == 0 && hs_out != nullptr && rin)
 #pragma unroll
       for (int s = 0; s < 4; ++s) *reinterpret_cast<bf16x8*>(hs_out + (long long)gr * C + 16 * s + 8 * hh) = hb[s];
@@ -209,15 +196,7 @@ __global__ __launch_bounds__(256) void ce2_fwd_kernel(const float* __restrict__ 
       // register i: vocab 32vb + acc_row(i, hh) of the chunk; the accumulator starts at the bias,
       // so the MFMAs add it (no per-logit VALU add) and the logit stays in natural units until
       // the exp2 argument (one fma)
-      f32x16 st;
-      {
-        const float* bp = sB[buf] + 32 * vb + 4 * hh;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const float4 bb = *reinterpret_cast<const float4*>(bp + 8 * q);
-          st[4 * q] = bb.x; st[4 * q + 1] = bb.y; st[4 * q + 2] = bb.z; st[4 * q + 3] = bb.w;
-        }
-      }
+      f32x16 st = bias_acc(sB[buf] + 32 * vb + 4 * hh);
 #pragma unroll
       for (int s = 0; s < 4; ++s) st = mfma32(ce2::img_kc(img, 32 * vb, s), hb[s], st);
       // p against the running reference max; a tile whose sum leaves [0, 2^kRescale] (a logit
@@ -565,16 +544,19 @@ __global__ __launch_bounds__(256) void ce2_bwd_kernel(const uint16_t* __restrict
 }
 
 // ---- host side --------------------------------------------------------------------------
-int ce2_num_splits(int M, int V) {
-  // ≈ 2 workgroups per CU over (row blocks × vocab splits); every split ≥ 4 chunks
-  const int rb = (M + ce2::RB - 1) / ce2::RB, nchunks = (V + ce2::VC - 1) / ce2::VC;
+int vocab_splits(int M, int V, int rows_per_wg, int chunk, int max_splits) {
+  const int rb = (M + rows_per_wg - 1) / rows_per_wg, nchunks = (V + chunk - 1) / chunk;
   int s = (512 + rb - 1) / rb;
   s = s < 1 ? 1 : s;
   const int cap = (nchunks + 3) / 4;
   s = s > cap ? cap : s;
-  s = s > ce2::kCeMaxSplitsFwd ? ce2::kCeMaxSplitsFwd : s;
+  s = s > max_splits ? max_splits : s;
   const int cps = (nchunks + s - 1) / s;
   return (nchunks + cps - 1) / cps;
+}
+CeFwdPlan ce2_fwd_plan(int M, int V) {
+  const int nrb = (M + ce2::RB - 1) / ce2::RB;  // a loss partial pair and an arrival counter per row block
+  return CeFwdPlan{vocab_splits(M, V, ce2::RB, ce2::VC, ce2::kCeMaxSplitsFwd), true, nrb, nrb};
 }
 int ce2_bwd_splits(int M, int V) {
   // row splits of pass 2: ≈ 512 workgroups, every split ≥ 4 tiles (the slab height)
@@ -586,41 +568,34 @@ int ce2_bwd_splits(int M, int V) {
   const int tps = (nt + s - 1) / s;
   return (nt + tps - 1) / tps;
 }
-int ce2_row_blocks(int M) { return (M + ce2::RB - 1) / ce2::RB; }
 
-void ce2_fwd_launch(const float* Hm, const int64_t* hidx, const int64_t* labels, const uint16_t* W, const float* bias,
-                    int M, int V, int nsplit, float2* part_ml, float* part_acc, float* picked, uint16_t* hs_out,
-                    float* lse, float* count, int count_labels, float* loss, float* blk, unsigned* rb_ticket,
-                    unsigned* ticket, float* zero_out, long long zero_n, hipStream_t st) {
-  const int nchunks = (V + ce2::VC - 1) / ce2::VC;
-  const int cps = (nchunks + nsplit - 1) / nsplit;
-  hipLaunchKernelGGL(ce2_fwd_kernel, dim3(ce2_row_blocks(M), nsplit), dim3(256), 0, st, Hm, hidx, labels, W, bias, M, V,
-                     cps, part_ml, part_acc, picked, hs_out, lse, count, count_labels, loss, blk, rb_ticket, ticket,
-                     zero_out, zero_n / 4);
+void ce2_fwd_launch(const CeFwdArgs& a, hipStream_t st) {
+  const int nchunks = (a.V + ce2::VC - 1) / ce2::VC;
+  const int cps = (nchunks + a.nsplit - 1) / a.nsplit;
+  hipLaunchKernelGGL(ce2_fwd_kernel, dim3((a.M + ce2::RB - 1) / ce2::RB, a.nsplit), dim3(256), 0, st, a.H, a.hidx,
+                     a.labels, a.W, a.bias, a.M, a.V, cps, reinterpret_cast<float2*>(a.part_ml), a.part_acc, a.picked,
+                     a.hs, a.lse, a.count, a.count_labels, a.loss, a.blk, a.rb_tickets, a.ticket, a.zero_out,
+                     a.zero_n / 4);
 }
 
-void ce2_bwd_launch(const uint16_t* Hs, const int64_t* labels, const uint16_t* W, const float* bias, const float* lse,
-                    const float* part_acc, const float2* part_ml, int nsplit, const float* gout, const float* count,
-                    int M, int V, float* dW, float* db, float* slab, int accumulate, float* dH, long long dh_rows,
-                    const int64_t* rowmap, hipStream_t st) {
+void ce2_bwd_launch(const CeBwdArgs& a, hipStream_t st) {
+  const int M = a.M, V = a.V;
   const int rsplit = ce2_bwd_splits(M, V);
   const int nt = (M + ce2::HT - 1) / ce2::HT;
   const int tps = (nt + rsplit - 1) / rsplit;
-  if (!accumulate && slab == nullptr) {
-    (void)hipMemsetAsync(dW, 0, sizeof(float) * (size_t)V * ce2::C, st);
-    (void)hipMemsetAsync(db, 0, sizeof(float) * (size_t)V, st);
+  if (!a.accumulate && a.slab == nullptr) {
+    (void)hipMemsetAsync(a.dW, 0, sizeof(float) * (size_t)V * ce2::C, st);
+    (void)hipMemsetAsync(a.db, 0, sizeof(float) * (size_t)V, st);
   }
   const int vb = (V + ce2::VB2 - 1) / ce2::VB2;
   // appended dH grid rows: one row (vb workgroups) at a wide vocabulary — more cost the MLM head
   // 3 µs (31.7 → 34.9 µs, r6) — and ≈ kDhRowsPerWg rows per workgroup at a classifier's few blocks
   const int ndh = (M + ce2::kDhRowsPerWg - 1) / ce2::kDhRowsPerWg;
   const int ndy = vb >= 16 ? 1 : std::max(1, (ndh + vb - 1) / vb);
-  if (V <= ce2::kOneHotInTileMaxV)
-    hipLaunchKernelGGL(ce2_bwd_kernel<true>, dim3(vb, rsplit + ndy), dim3(256), 0, st, Hs, labels, W, bias, lse, part_acc,
-                       part_ml, nsplit, gout, count, M, V, rsplit, tps, dW, db, slab, dH, rowmap, dh_rows);
-  else
-    hipLaunchKernelGGL(ce2_bwd_kernel<false>, dim3(vb, rsplit + ndy), dim3(256), 0, st, Hs, labels, W, bias, lse, part_acc,
-                       part_ml, nsplit, gout, count, M, V, rsplit, tps, dW, db, slab, dH, rowmap, dh_rows);
+  const auto kernel = V <= ce2::kOneHotInTileMaxV ? ce2_bwd_kernel<true> : ce2_bwd_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3(vb, rsplit + ndy), dim3(256), 0, st, a.hs, a.labels, a.W, a.bias, a.lse, a.part_acc,
+                     reinterpret_cast<const float2*>(a.part_ml), a.nsplit, a.gout, a.count, M, V, rsplit, tps, a.dW, a.db,
+                     a.slab, a.dH, a.rowmap, a.dh_rows);
 }
 
 unsigned check_errors_ce_head(bool reset) { return pio_read_errors(reset); }

@@ -300,6 +300,68 @@ struct AttnBwdArgs {
   int dq_zeroed;                // attn_bwd_zero_plan bits the caller has already cleared
 };
 
+// ---- arguments of the vocabulary heads (ce_head.hip, mlm_head.hip, soft_ce_head.hip, topk_head.hip)
+// W (V, C) bf16 and bias (V) fp32 throughout.
+// mean CE over the M rows with a label >= 0; row r = H[hidx[r]] (hidx null: H[r]) of the fp32 H
+struct CeFwdArgs {
+  int C, M, V;
+  const float* H; const int64_t* hidx;
+  const int64_t* labels;
+  const uint16_t* W; const float* bias;
+  float *loss, *lse;            // the mean loss (1) and the rows' log-sum-exp (M)
+  uint16_t* hs;                 // the compact bf16 rows (M, C) the backward reads
+  float* count; int count_labels;  // the mean's denominator: read, or (count_labels) counted and written
+  // workspace, sized by ce_fwd_plan
+  int nsplit;
+  float* part_ml;               // (nsplit, M, 2) the splits' (max, sum)
+  float* part_acc;              // (nsplit, M, C) the splits' Σ p·W (plan.acc), kept for the backward
+  float *picked, *blk;          // (M), (2·plan.nblk)
+  unsigned *ticket, *rb_tickets;  // one zeroed word, plan.rb_tickets zeroed words: re-armed by the kernels
+  float* zero_out; long long zero_n;  // cleared on the way (null: nothing); 16-byte aligned, zero_n % 4 == 0
+};
+struct CeFwdPlan {
+  int nsplit;      // vocab splits
+  bool acc;        // the two-pass head (C = 64): part_acc exists and goes to the backward with part_ml
+  int nblk;        // block partials of the loss
+  int rb_tickets;  // row-block arrival counters needed (0: none)
+};
+// dH[rowmap[r]] (rowmap null: dH[r]) += the row gradients, dW / db (+)= the parameter gradients of
+// the mean loss's gradient gout; hs, lse, count (and part_acc / part_ml, nsplit at C = 64) from the forward
+struct CeBwdArgs {
+  int C, M, V;
+  const uint16_t* hs;
+  const int64_t* labels;
+  const uint16_t* W; const float* bias;
+  const float *lse, *gout, *count;
+  const float *part_acc, *part_ml; int nsplit;
+  float* dH; long long dh_rows; const int64_t* rowmap;
+  float *dW, *db; int accumulate;
+  float* slab;                  // (ce_bwd_slab_rows, V·C + V₄) dW | db partials stored, not added; or null
+  int det;                      // deterministic mode: the generic head's dH pass runs one vocab split
+};
+// the soft-target head, both directions.  Forward: H (M, C) fp32 in; lse, pred, hs, loss, count out,
+// blk (2·soft_ce_row_tiles) scratch.  Backward: hs, lse, count, gout in; dH overwritten, dW / db
+// overwritten or (accumulate) added to.
+struct SoftCeArgs {
+  int C, M, V;
+  const uint16_t* W; const float* bias;
+  const int64_t *la, *lb; const float* lam; float eps;
+  const float* H;
+  uint16_t* hs; float *lse, *count;
+  int* pred; float *blk, *loss;
+  const float* gout; float *dH, *dW, *db; int accumulate;
+};
+// the k largest logits of M rows (row r = H[hidx[r]], hidx null: H[r]; H has R rows): C ∈ {64, 128},
+// 1 ≤ k ≤ 8, k ≤ V, M ≥ 1; nsplit = vocab_topk_splits, cand_v / cand_i hold nsplit·M·vocab_topk_kt(k)
+// entries, part_ml nsplit·M·2
+struct VocabTopkArgs {
+  int C, M, V, k;
+  const float* H; const int64_t* hidx; long long R;
+  const uint16_t* W; const float* bias;
+  int nsplit; float* cand_v; int* cand_i; float* part_ml;
+  float* values; int64_t* indices; float* lse;
+};
+
 // ---- attention.hip ----
 void attn_fwd_launch(const AttnArgs& a, int D, uint16_t* O, float* LSE, float* Opart, float* MLpart, int nsplit,
                      hipStream_t st);
@@ -347,18 +409,14 @@ void attn_weights_launch(const AttnArgs& a, int D, const float* LSE, float* avg,
 void batch_augment_launch(const uint8_t* src, const float* params, float* out, int B, int Hs, int Ws, int C, int oh,
                           int ow, const float* mean, const float* std, hipStream_t st);
 unsigned check_errors_augment(bool reset);
-// ---- ce_head.hip ----
-int ce2_num_splits(int M, int V);
+// ---- ce_head.hip (the two-pass head, C = 64; called by mlm_head.hip's launchers) ----
+// vocab splits of a (row blocks × vocab splits) grid: ≈ 512 workgroups (2 per CU), every split ≥ 4
+// chunks, at most max_splits; rounded so that no split is left without a chunk
+int vocab_splits(int M, int V, int rows_per_wg, int chunk, int max_splits);
+CeFwdPlan ce2_fwd_plan(int M, int V);
 int ce2_bwd_splits(int M, int V);
-int ce2_row_blocks(int M);
-void ce2_fwd_launch(const float* Hm, const int64_t* hidx, const int64_t* labels, const uint16_t* W, const float* bias,
-                    int M, int V, int nsplit, float2* part_ml, float* part_acc, float* picked, uint16_t* hs_out,
-                    float* lse, float* count, int count_labels, float* loss, float* blk, unsigned* rb_ticket,
-                    unsigned* ticket, float* zero_out, long long zero_n, hipStream_t st);
-void ce2_bwd_launch(const uint16_t* Hs, const int64_t* labels, const uint16_t* W, const float* bias, const float* lse,
-                    const float* part_acc, const float2* part_ml, int nsplit, const float* gout, const float* count,
-                    int M, int V, float* dW, float* db, float* slab, int accumulate, float* dH, long long dh_rows,
-                    const int64_t* rowmap, hipStream_t st);
+void ce2_fwd_launch(const CeFwdArgs& a, hipStream_t st);
+void ce2_bwd_launch(const CeBwdArgs& a, hipStream_t st);
 unsigned check_errors_ce_head(bool reset);
 // ---- chain.hip (called by rowgemm.hip's launchers once the operands qualify: C = 64, H = 4,
 // every pointer 16-byte aligned, R % 64 == 0) ----
@@ -448,23 +506,19 @@ struct EventCompactArgs {
 };
 void event_compact_launch(const EventCompactArgs& a, hipStream_t st);
 unsigned check_errors_lartpc_prep(bool reset);
-// ---- mlm_head.hip ----
+// ---- mlm_head.hip (the CE head's entry points; its own kernels are the generic head, C = 32 / 128;
+// C = 64 goes to ce_head.hip) ----
+CeFwdPlan ce_fwd_plan(int C, int M, int V);
+// rows of the backward's slab (the row splits of its dW pass)
+int ce_bwd_slab_rows(int C, int M, int V);
+void ce_fwd_launch(const CeFwdArgs& a, hipStream_t st);
+void ce_bwd_launch(const CeBwdArgs& a, hipStream_t st);
+unsigned check_errors_mlm_head(bool reset);
+// ---- mlm_select.hip ----
 void mlm_select_launch(const int64_t* labels, int B, int L, int cap, int gcap, int64_t* idx_b, int64_t* lab_b,
                        int* count, int64_t* gidx, int64_t* glab, float* total, bool* overflow, bool* sticky,
                        const float* P, int C, float* q, hipStream_t st);
-// tickets: one zeroed counter (the combine kernel's)
-void ce_fwd_launch(int C, const float* Hm, const int64_t* hidx, const int64_t* labels, const uint16_t* W,
-                   const float* bias, int M, int V, float* part_ms, float* picked, float* lse, float* count,
-                   float* loss, float* blk, unsigned* tickets, uint16_t* hs_out, int nsplit, float* zero_out,
-                   long long zero_n, int count_labels, hipStream_t st);
-int ce_combine_blocks(int M);
-int ce_num_splits(int M, int V);
-// row splits of the dW kernel (≈ 4 workgroups per CU): the slab height in slab mode
-int ce_dw_splits(int M, int V);
-void ce_bwd_launch(int C, const uint16_t* Hm, const int64_t* labels, const uint16_t* W, const float* bias,
-                   const float* lse, const float* gout, const float* count, int M, int V, float* dH, long long dh_rows,
-                   const int64_t* rowmap, float* dW, float* db, int accumulate, float* slab, int det, hipStream_t st);
-unsigned check_errors_mlm_head(bool reset);
+unsigned check_errors_mlm_select(bool reset);
 // ---- optim.hip ----
 void sumsq_launch(const float* g, long long n, float* part, hipStream_t st);
 void adamw_launch(float* p, float* g, float* m, float* v, uint16_t* shadow, long long n, const float* hyper,
@@ -550,23 +604,15 @@ bool sb_bwd_launch(const SBBwdArgs& a, int C, hipStream_t st);
 bool sb_wgrad_launch(SBWgradArgs a, int C, const SlabJob& sj, hipStream_t st);
 // ---- soft_ce_head.hip ----
 int soft_ce_row_tiles(int M);
-void soft_ce_fwd_launch(int C, const float* Hm, const uint16_t* W, const float* bias, const int64_t* la,
-                        const int64_t* lb, const float* lam, float eps, int M, int V, float* lse, int* pred,
-                        uint16_t* hs, float* blk, float* loss, float* count, hipStream_t st);
-void soft_ce_bwd_launch(int C, const uint16_t* Hs, const uint16_t* W, const float* bias, const int64_t* la,
-                        const int64_t* lb, const float* lam, float eps, const float* lse, const float* gout,
-                        const float* count, int M, int V, float* dH, float* dW, float* db, int accumulate,
-                        hipStream_t st);
+void soft_ce_fwd_launch(const SoftCeArgs& a, hipStream_t st);
+void soft_ce_bwd_launch(const SoftCeArgs& a, hipStream_t st);
 void batch_mix_launch(const float* x, const int64_t* y, const float* mix, float* out, int64_t* yb, float* lam_out, int B,
                       int H, int W, int Ch, hipStream_t st);
 unsigned check_errors_soft_ce_head(bool reset);
 // ---- topk_head.hip ----
 int vocab_topk_splits(int M, int V);
 int vocab_topk_kt(int k);
-// C ∈ {64, 128}, 1 ≤ k ≤ 8, k ≤ V, M ≥ 1; cand_v / cand_i hold nsplit·M·vocab_topk_kt(k) entries
-void vocab_topk_launch(int C, const float* Hm, const int64_t* hidx, long long R, const uint16_t* W, const float* bias,
-                       int M, int V, int k, int nsplit, float* cand_v, int* cand_i, float2* part_ml, float* values,
-                       int64_t* indices, float* lse, hipStream_t st);
+void vocab_topk_launch(const VocabTopkArgs& a, hipStream_t st);
 unsigned check_errors_topk_head(bool reset);
 
 }  // namespace pio

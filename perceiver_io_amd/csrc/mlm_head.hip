@@ -11,9 +11,10 @@
 //   bwd-b: dW  = (softmax − onehot)ᵀ·g · H, db = Σ rows   (vocab chunk × row split, fp32 atomics)
 // Streamed operands (W chunks, H tiles) are register-prefetched one tile ahead.
 // Only the ~15 % masked positions are ever passed in (rows compacted on device).
-#include <cstdlib>
-
+// These are the generic kernels (C = 32 / 128).  The head's host entry points at the end of the file
+// hand C = 64 to the two-pass head (ce_head.hip); the row selection is mlm_select.hip.
 #include "common.h"
+#include "head_common.h"
 
 namespace pio {
 
@@ -27,8 +28,6 @@ constexpr int VB = 64;  // vocab entries per tile
 // work inside the vocab loop: one max over 16 registers, one rescale exp per tile, and one
 // v_exp_f32 per logit (log2 domain) — ≈4 VALU instructions per logit instead of ≈20.
 // A = W chunk [v][c], B = H tile [r][c] (both k-contiguous).
-constexpr float kL2E = 1.4426950408889634f;
-constexpr float kLN2 = 0.6931471805599453f;
 template <int C>
 __device__ __forceinline__ f32x16 logits_tile_t(const uint16_t* sH, const uint16_t* sW, int ld) {
   const int w = wave_id();
@@ -40,12 +39,9 @@ __device__ __forceinline__ f32x16 logits_tile_t(const uint16_t* sH, const uint16
 // the 16 per-register values of a 64-entry LDS vector (vocab-indexed) for this lane:
 // register i <-> entry 32(w & 1) + 4h + (i & 3) + 8(i >> 2): four 16-byte reads
 __device__ __forceinline__ void vocab_regs(const float* sv, float (&out)[16]) {
-  const float* p = sv + 32 * (wave_id() & 1) + 4 * (lane_id() >> 5);
+  const f32x16 v = bias_acc(sv + 32 * (wave_id() & 1) + 4 * (lane_id() >> 5));
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const float4 v = *reinterpret_cast<const float4*>(p + 8 * q);
-    out[4 * q] = v.x; out[4 * q + 1] = v.y; out[4 * q + 2] = v.z; out[4 * q + 3] = v.w;
-  }
+  for (int i = 0; i < 16; ++i) out[i] = v[i];
 }
 // register of this lane holding entry j of the wave's 32-entry vocab block, or -1
 __device__ __forceinline__ int vocab_reg(int j) {
@@ -521,141 +517,6 @@ __global__ __launch_bounds__(256) void ce_bwd_dw_reg_kernel(const uint16_t* __re
   }
 }
 
-// ------------------------------------------------------------------------------------
-// selected-position bookkeeping for the MLM loss (replaces ~15 small framework kernels)
-//   rows  : per sequence b, slots [0, cap): positions of labels != -100 in order (unused
-//           slots → slot mod L, label −100), count[b]
-//   global: the valid slots of all sequences compacted into gcap rows for the vocab GEMMs
-//           (unused → slot 0 with label −100), total = Σ count (the mean's denominator)
-// ------------------------------------------------------------------------------------
-// select_rows: workgroup b compacts sequence b.  select_global, workgroup (b, 0): finds sequence
-// b's offset in the global rows from all the per-sequence counts (each workgroup scans them
-// itself: no grid-wide hand-off) and writes its valid slots; workgroup (0, 0) also writes the
-// totals, the last one the unused tail.  Every workgroup (b, y) also copies the output-query rows
-// q[b, j] = P[idx_b[b, j]] of its kSelSlots slots (the gather of the decoder's query array,
-// spread over the whole grid).
-constexpr int kSelThreads = 1024;
-constexpr int kSelSlots = 128;  // query-gather slots per select_global workgroup
-__global__ __launch_bounds__(kSelThreads) void select_rows_kernel(const int64_t* __restrict__ labels, int L, int cap,
-                                                                  int64_t* __restrict__ idx_b, int64_t* __restrict__ lab_b,
-                                                                  int* __restrict__ count) {
-  __shared__ int sW[kSelThreads / 64], sOff;
-  const int b = blockIdx.x, w = wave_id(), l = lane_id(), nw = blockDim.x >> 6;
-  if (threadIdx.x == 0) sOff = 0;
-  lds_sync();
-  for (int c0 = 0; c0 < L; c0 += blockDim.x) {
-    const int i = c0 + threadIdx.x;
-    const int64_t lab = i < L ? labels[(long long)b * L + i] : -100;
-    const bool sel = lab != -100;
-    const uint64_t m = __ballot(sel);
-    const int pre = __popcll(m & ((1ull << l) - 1ull));
-    if (l == 0) sW[w] = __popcll(m);
-    lds_sync();
-    int woff = 0, tot = 0;
-    for (int k = 0; k < nw; ++k) {
-      woff += k < w ? sW[k] : 0;
-      tot += sW[k];
-    }
-    const int pos = sOff + woff + pre;
-    if (sel && pos < cap) {
-      idx_b[(long long)b * cap + pos] = i;
-      lab_b[(long long)b * cap + pos] = lab;
-    }
-    lds_sync();
-    if (threadIdx.x == 0) sOff += tot;
-    lds_sync();
-  }
-  const int cnt = sOff;
-  for (int j = (cnt < cap ? cnt : cap) + threadIdx.x; j < cap; j += blockDim.x) {
-    idx_b[(long long)b * cap + j] = j % L;
-    lab_b[(long long)b * cap + j] = -100;
-  }
-  if (threadIdx.x == 0) count[b] = cnt;
-}
-
-__device__ __forceinline__ int wave_isum(int v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-
-__global__ __launch_bounds__(256) void select_global_kernel(const int* __restrict__ count, int B, int cap,
-                                                            const int64_t* __restrict__ lab_b, int gcap,
-                                                            int64_t* __restrict__ gidx, int64_t* __restrict__ glab,
-                                                            float* __restrict__ total, bool* __restrict__ overflow,
-                                                            bool* __restrict__ sticky, const int64_t* __restrict__ idx_b,
-                                                            const float* __restrict__ P, int C, float* __restrict__ q) {
-  __shared__ int sRed[4][4];
-  __shared__ long long sI[kSelSlots];
-  const int b = blockIdx.x, w = wave_id(), l = lane_id();
-  if (q != nullptr) {  // slots [kSelSlots·y, +kSelSlots) of sequence b: q[b, j] = P[idx_b[b, j]]
-    const int C4 = C >> 2, j0 = blockIdx.y * kSelSlots, nj = min(cap - j0, kSelSlots);
-    const float4* P4 = reinterpret_cast<const float4*>(P);
-    float4* q4 = reinterpret_cast<float4*>(q) + ((long long)b * cap + j0) * C4;
-    for (int j = threadIdx.x; j < nj; j += blockDim.x) sI[j] = idx_b[(long long)b * cap + j0 + j];
-    __syncthreads();
-    for (int e0 = 0; e0 < nj * C4; e0 += 8 * 256) {  // eight independent row loads in flight per thread
-      float4 v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int e = e0 + u * 256 + threadIdx.x;
-        if (e < nj * C4) {
-          const int j = e / C4;
-          v[u] = P4[sI[j] * C4 + (e - j * C4)];
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int e = e0 + u * 256 + threadIdx.x;
-        if (e < nj * C4) q4[e] = v[u];
-      }
-    }
-  }
-  if (blockIdx.y != 0) return;
-  int pre = 0, used = 0, all = 0, ovf = 0;
-  for (int i = threadIdx.x; i < B; i += blockDim.x) {
-    const int c = count[i], n = c < cap ? c : cap;
-    pre += i < b ? n : 0;
-    used += n;
-    all += c;
-    ovf += c > cap ? 1 : 0;
-  }
-  pre = wave_isum(pre); used = wave_isum(used); all = wave_isum(all); ovf = wave_isum(ovf);
-  if (l == 0) { sRed[0][w] = pre; sRed[1][w] = used; sRed[2][w] = all; sRed[3][w] = ovf; }
-  __syncthreads();
-  pre = sRed[0][0] + sRed[0][1] + sRed[0][2] + sRed[0][3];
-  used = sRed[1][0] + sRed[1][1] + sRed[1][2] + sRed[1][3];
-  const int c = count[b], n = c < cap ? c : cap;
-  for (int j = threadIdx.x; j < n; j += blockDim.x) {
-    const int g = pre + j;
-    if (g < gcap) {
-      const long long s = (long long)b * cap + j;
-      gidx[g] = s;
-      glab[g] = lab_b[s];
-    }
-  }
-  if (b == B - 1)
-    for (int g = (used < gcap ? used : gcap) + threadIdx.x; g < gcap; g += blockDim.x) {
-      gidx[g] = 0;
-      glab[g] = -100;
-    }
-  if (b == 0 && threadIdx.x == 0) {
-    const bool o = (sRed[3][0] + sRed[3][1] + sRed[3][2] + sRed[3][3]) > 0 || used > gcap;
-    total[0] = (float)(sRed[2][0] + sRed[2][1] + sRed[2][2] + sRed[2][3]);
-    overflow[0] = o;
-    if (sticky != nullptr && o) sticky[0] = true;  // the persistent per-device flag (never cleared here)
-  }
-}
-
-void mlm_select_launch(const int64_t* labels, int B, int L, int cap, int gcap, int64_t* idx_b, int64_t* lab_b,
-                       int* count, int64_t* gidx, int64_t* glab, float* total, bool* overflow, bool* sticky,
-                       const float* P, int C, float* q, hipStream_t st) {
-  hipLaunchKernelGGL(select_rows_kernel, dim3(B), dim3(kSelThreads), 0, st, labels, L, cap, idx_b, lab_b, count);
-  const int gy = q ? (cap + kSelSlots - 1) / kSelSlots : 1;
-  hipLaunchKernelGGL(select_global_kernel, dim3(B, gy), dim3(256), 0, st, count, B, cap, lab_b, gcap, gidx, glab, total,
-                     overflow, sticky, idx_b, P, C, q);
-}
-
 // vocab splits so that a launch has ≈ target workgroups (several per CU hide the W-chunk latency);
 // rounded so that every split owns at least one chunk (ceil(nchunks / ceil(nchunks / s)) splits)
 static int pick_split(int M, int nchunks, int target) {
@@ -666,74 +527,69 @@ static int pick_split(int M, int nchunks, int target) {
   return (nchunks + cps - 1) / cps;
 }
 
-// workgroup targets of the three CE launches (the C = 32 / 128 heads; C = 64 runs ce_head.hip)
-static int ce_target(const char*, int dflt) { return dflt; }
-
-// tickets: one zeroed counter (the combine kernel's)
-void ce_fwd_launch(int C, const float* Hm, const int64_t* hidx, const int64_t* labels, const uint16_t* W,
-                   const float* bias, int M, int V, float* part_ms, float* picked, float* lse, float* count,
-                   float* loss, float* blk, unsigned* tickets, uint16_t* hs_out, int nsplit, float* zero_out,
-                   long long zero_n, int count_labels, hipStream_t st) {
-  const int nchunks = (V + VB - 1) / VB;
-  const int cps = (nchunks + nsplit - 1) / nsplit;
-  dim3 grid((M + HB - 1) / HB, nsplit);
-#define CEF(CC)                                                                                                 \
-  hipLaunchKernelGGL(ce_fwd_kernel<CC>, grid, dim3(256), 0, st, Hm, hidx, labels, W, bias, M, V, cps, part_ms, picked, \
-                     hs_out, zero_out, zero_n / 4)
-  if (C == 64) { CEF(64); }
-  else if (C == 128) { CEF(128); }
-  else if (C == 32) { CEF(32); }
-#undef CEF
-  hipLaunchKernelGGL(ce_combine_kernel, dim3(ce_combine_blocks(M)), dim3(kCombineRows * kCombineQ), 0, st, part_ms, picked,
-                     labels, M, nsplit,
-                     lse, count, loss, blk, tickets, count_labels);
-}
-
-int ce_combine_blocks(int M) { return (M + kCombineRows - 1) / kCombineRows; }
-
-int ce_num_splits(int M, int V) { return pick_split(M, (V + VB - 1) / VB, ce_target("PIO_CE_FWD_WGS", 2048)); }
-
 // row splits of the dW kernel (≈ 4 workgroups per CU): the slab height in slab mode
-int ce_dw_splits(int M, int V) {
+static int ce_dw_splits(int M, int V) {
   const int nchunks = (V + VB - 1) / VB, mtiles = (M + HB - 1) / HB;
-  int rsplit = (ce_target("PIO_CE_DW_WGS", 1024) + nchunks - 1) / nchunks;
+  int rsplit = (1024 + nchunks - 1) / nchunks;
   rsplit = rsplit < 1 ? 1 : (rsplit > mtiles ? mtiles : rsplit);
   const int tps = (mtiles + rsplit - 1) / rsplit;
   return (mtiles + tps - 1) / tps;
 }
 
-void ce_bwd_launch(int C, const uint16_t* Hm, const int64_t* labels, const uint16_t* W,
-                   const float* bias, const float* lse, const float* gout, const float* count, int M, int V, float* dH, long long dh_rows, const int64_t* rowmap, float* dW,
-                   float* db, int accumulate, float* slab, int det, hipStream_t st) {
-  const int nchunks = (V + VB - 1) / VB;
+// workgroup targets of the three launches of the generic head: 2048 for the forward, 1024 for the dW
+// and the dH kernel
+CeFwdPlan ce_fwd_plan(int C, int M, int V) {
+  if (C == 64) return ce2_fwd_plan(M, V);
+  return CeFwdPlan{pick_split(M, (V + VB - 1) / VB, 2048), false, (M + kCombineRows - 1) / kCombineRows, 0};
+}
+int ce_bwd_slab_rows(int C, int M, int V) { return C == 64 ? ce2_bwd_splits(M, V) : ce_dw_splits(M, V); }
+
+// the generic head's kernels at width C
+template <int C>
+static void ce_fwd_run(const CeFwdArgs& a, int cps, hipStream_t st) {
+  hipLaunchKernelGGL(ce_fwd_kernel<C>, dim3((a.M + HB - 1) / HB, a.nsplit), dim3(256), 0, st, a.H, a.hidx, a.labels, a.W,
+                     a.bias, a.M, a.V, cps, a.part_ml, a.picked, a.hs, a.zero_out, a.zero_n / 4);
+}
+template <int C>
+static void ce_bwd_run(const CeBwdArgs& a, dim3 ga, int cps, dim3 gb, int tps, hipStream_t st) {
+  hipLaunchKernelGGL(ce_bwd_dh_reg_kernel<C>, ga, dim3(256), 0, st, a.hs, a.labels, a.W, a.bias, a.lse, a.gout, a.count,
+                     a.M, a.V, cps, a.dH, a.rowmap, a.dh_rows);
+  hipLaunchKernelGGL(ce_bwd_dw_reg_kernel<C>, gb, dim3(256), 0, st, a.hs, a.labels, a.W, a.bias, a.lse, a.gout, a.count,
+                     a.M, a.V, tps, a.dW, a.db, a.slab);
+}
+
+void ce_fwd_launch(const CeFwdArgs& a, hipStream_t st) {
+  if (a.C == 64) return ce2_fwd_launch(a, st);
+  const int nchunks = (a.V + VB - 1) / VB;
+  const int cps = (nchunks + a.nsplit - 1) / a.nsplit;
+  if (a.C == 128) ce_fwd_run<128>(a, cps, st);
+  else ce_fwd_run<32>(a, cps, st);
+  hipLaunchKernelGGL(ce_combine_kernel, dim3((a.M + kCombineRows - 1) / kCombineRows), dim3(kCombineRows * kCombineQ), 0,
+                     st, a.part_ml, a.picked, a.labels, a.M, a.nsplit, a.lse, a.count, a.loss, a.blk, a.ticket,
+                     a.count_labels);
+}
+
+void ce_bwd_launch(const CeBwdArgs& a, hipStream_t st) {
+  if (a.C == 64) return ce2_bwd_launch(a, st);
+  const int M = a.M, V = a.V, nchunks = (V + VB - 1) / VB;
   // dH partials are added atomically: few splits; deterministic mode: one (a single writer per
   // dH element — every compacted row maps to its own source position)
-  const int nsplit = det ? 1 : pick_split(M, nchunks, ce_target("PIO_CE_DH_WGS", 1024));
+  const int nsplit = a.det ? 1 : pick_split(M, nchunks, 1024);
   const int cps = (nchunks + nsplit - 1) / nsplit;
   // dW: (vocab chunk × row split) workgroups, ≈ 4 per CU; dW / db partials added atomically
   // or stored into the slab
   const int mtiles = (M + HB - 1) / HB;
   const int rsplit = ce_dw_splits(M, V);
   const int tps = (mtiles + rsplit - 1) / rsplit;
-  if (!accumulate) {
-    (void)hipMemsetAsync(dW, 0, sizeof(float) * (size_t)V * C, st);
-    (void)hipMemsetAsync(db, 0, sizeof(float) * (size_t)V, st);
+  if (!a.accumulate) {
+    (void)hipMemsetAsync(a.dW, 0, sizeof(float) * (size_t)V * a.C, st);
+    (void)hipMemsetAsync(a.db, 0, sizeof(float) * (size_t)V, st);
   }
-  dim3 ga((M + HB - 1) / HB, nsplit), gb(nchunks, rsplit);
-#define CEB(CC)                                                                                                 \
-  hipLaunchKernelGGL(ce_bwd_dh_reg_kernel<CC>, ga, dim3(256), 0, st, Hm, labels, W, bias, lse, gout, count, M, V,   \
-                     cps, dH, rowmap, dh_rows);                                                                    \
-  hipLaunchKernelGGL(ce_bwd_dw_reg_kernel<CC>, gb, dim3(256), 0, st, Hm, labels, W, bias, lse, gout, count, M, V,   \
-                     tps, dW, db, slab)
-  if (C == 64) { CEB(64); }
-  else if (C == 128) { CEB(128); }
-  else if (C == 32) { CEB(32); }
-#undef CEB
+  if (a.C == 128) ce_bwd_run<128>(a, dim3(mtiles, nsplit), cps, dim3(nchunks, rsplit), tps, st);
+  else ce_bwd_run<32>(a, dim3(mtiles, nsplit), cps, dim3(nchunks, rsplit), tps, st);
 }
 
-}  // namespace pio
-
-namespace pio {
 unsigned check_errors_mlm_head(bool reset) { return pio_read_errors(reset); }
+
 }  // namespace pio
 

@@ -23,6 +23,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "head_common.h"
 
 namespace pio {
 
@@ -30,8 +31,6 @@ namespace sce {
 
 constexpr int RT = 32;  // rows per tile
 constexpr int NW = 4;   // waves per workgroup
-constexpr float kL2E = 1.4426950408889634f;
-constexpr float kLN2 = 0.6931471805599453f;
 
 // a row's label pair is usable: both inside [0, V) (label_a = -100: the row carries no loss)
 __device__ __forceinline__ bool labels_ok(int a, int b, int V) { return a >= 0 && a < V && b >= 0 && b < V; }
@@ -446,30 +445,19 @@ __global__ __launch_bounds__(256) void batch_mix_kernel(const float* __restrict_
 // ---- host side ----------------------------------------------------------------------------
 int soft_ce_row_tiles(int M) { return (M + sce::RT - 1) / sce::RT; }
 
-void soft_ce_fwd_launch(int C, const float* Hm, const uint16_t* W, const float* bias, const int64_t* la,
-                        const int64_t* lb, const float* lam, float eps, int M, int V, float* lse, int* pred,
-                        uint16_t* hs, float* blk, float* loss, float* count, hipStream_t st) {
-  const int nrt = soft_ce_row_tiles(M);
-  if (C == 64)
-    hipLaunchKernelGGL(soft_ce_fwd_kernel<64>, dim3(nrt), dim3(256), 0, st, Hm, W, bias, la, lb, lam, eps, M, V, lse,
-                       pred, hs, blk, loss, count);
-  else
-    hipLaunchKernelGGL(soft_ce_fwd_kernel<128>, dim3(nrt), dim3(256), 0, st, Hm, W, bias, la, lb, lam, eps, M, V, lse,
-                       pred, hs, blk, loss, count);
-  if (nrt > 1) hipLaunchKernelGGL(soft_ce_finish_kernel, dim3(1), dim3(64), 0, st, blk, nrt, loss, count);
+void soft_ce_fwd_launch(const SoftCeArgs& a, hipStream_t st) {
+  const int nrt = soft_ce_row_tiles(a.M);
+  const auto kernel = a.C == 64 ? soft_ce_fwd_kernel<64> : soft_ce_fwd_kernel<128>;
+  hipLaunchKernelGGL(kernel, dim3(nrt), dim3(256), 0, st, a.H, a.W, a.bias, a.la, a.lb, a.lam, a.eps, a.M, a.V, a.lse,
+                     a.pred, a.hs, a.blk, a.loss, a.count);
+  if (nrt > 1) hipLaunchKernelGGL(soft_ce_finish_kernel, dim3(1), dim3(64), 0, st, a.blk, nrt, a.loss, a.count);
 }
 
-void soft_ce_bwd_launch(int C, const uint16_t* Hs, const uint16_t* W, const float* bias, const int64_t* la,
-                        const int64_t* lb, const float* lam, float eps, const float* lse, const float* gout,
-                        const float* count, int M, int V, float* dH, float* dW, float* db, int accumulate,
-                        hipStream_t st) {
-  const int nrt = soft_ce_row_tiles(M), nvt = (V + 31) / 32;
-  if (C == 64)
-    hipLaunchKernelGGL(soft_ce_bwd_kernel<64>, dim3(nrt + nvt), dim3(256), 0, st, Hs, W, bias, la, lb, lam, eps, lse,
-                       gout, count, M, V, nrt, dH, dW, db, accumulate);
-  else
-    hipLaunchKernelGGL(soft_ce_bwd_kernel<128>, dim3(nrt + nvt), dim3(256), 0, st, Hs, W, bias, la, lb, lam, eps, lse,
-                       gout, count, M, V, nrt, dH, dW, db, accumulate);
+void soft_ce_bwd_launch(const SoftCeArgs& a, hipStream_t st) {
+  const int nrt = soft_ce_row_tiles(a.M), nvt = (a.V + 31) / 32;
+  const auto kernel = a.C == 64 ? soft_ce_bwd_kernel<64> : soft_ce_bwd_kernel<128>;
+  hipLaunchKernelGGL(kernel, dim3(nrt + nvt), dim3(256), 0, st, a.hs, a.W, a.bias, a.la, a.lb, a.lam, a.eps, a.lse,
+                     a.gout, a.count, a.M, a.V, nrt, a.dH, a.dW, a.db, a.accumulate);
 }
 
 void batch_mix_launch(const float* x, const int64_t* y, const float* mix, float* out, int64_t* yb, float* lam_out, int B,

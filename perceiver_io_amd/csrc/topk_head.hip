@@ -27,6 +27,7 @@
 // fragments of 16 consecutive rows then start 36 (C = 64) or 68 (C = 128) banks apart and cover
 // all 64 banks once.
 #include "common.h"
+#include "head_common.h"
 
 namespace pio {
 
@@ -37,8 +38,6 @@ constexpr int VC = 64;         // vocab entries per staged chunk
 constexpr int kMaxSplits = 16; // vocab splits (grid.y) at most
 constexpr int kMaxK = 8;
 constexpr int kNoIndex = 0x7fffffff;  // index of an empty candidate slot (value −inf): loses every tie
-constexpr float kL2E = 1.4426950408889634f;
-constexpr float kLN2 = 0.6931471805599453f;
 
 __device__ __forceinline__ bool beats(float a, int ai, float b, int bi) { return a > b || (a == b && ai < bi); }
 
@@ -55,15 +54,6 @@ __device__ __forceinline__ void insert(float (&tv)[KT], int (&ti)[KT], float x, 
     tv[j] = b1 ? tv[jm] : (b0 ? x : tv[j]);
     ti[j] = b1 ? ti[jm] : (b0 ? xi : ti[j]);
   }
-}
-
-// (m, l) ← the log2-domain (max, Σ 2^(t − max)) pairs (m, l) and (om, ol) merged; an empty side
-// has m = −inf, l = 0
-__device__ __forceinline__ void merge_ml(float& m, float& l, float om, float ol) {
-  const float mn = fmaxf(m, om);
-  const float ms = mn == -__builtin_inff() ? 0.f : mn;
-  l = l * fast_exp2(m - ms) + ol * fast_exp2(om - ms);
-  m = mn;
 }
 
 }  // namespace vtk
@@ -103,19 +93,7 @@ __global__ __launch_bounds__(256) void vocab_topk_kernel(const float* __restrict
 #else
     (void)R;
 #endif
-    const float* hp = Hm + src * C + 8 * hh;
-    float4 a[KS], b[KS];
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      a[s] = *reinterpret_cast<const float4*>(rin ? hp + 16 * s : kZero32B);
-      b[s] = *reinterpret_cast<const float4*>(rin ? hp + 16 * s + 4 : kZero32B);
-    }
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      hb[s][0] = (short)f2bf(a[s].x); hb[s][1] = (short)f2bf(a[s].y); hb[s][2] = (short)f2bf(a[s].z);
-      hb[s][3] = (short)f2bf(a[s].w); hb[s][4] = (short)f2bf(b[s].x); hb[s][5] = (short)f2bf(b[s].y);
-      hb[s][6] = (short)f2bf(b[s].z); hb[s][7] = (short)f2bf(b[s].w);
-    }
+    load_row_operand(hb, Hm + src * C + 8 * hh, rin);
   }
   // chunk staging: 64 vocab rows × SL slots of 16 bytes, NP per thread (+ the bias)
   bf16x8 wr[NP];
@@ -156,15 +134,7 @@ __global__ __launch_bounds__(256) void vocab_topk_kernel(const float* __restrict
 #pragma unroll
     for (int vb = 0; vb < 2; ++vb) {  // two 32-vocab blocks per chunk
       // register i: vocab c·64 + 32vb + acc_row(i, hh); the accumulator starts at the bias
-      f32x16 st;
-      {
-        const float* bp = sB[buf] + 32 * vb + 4 * hh;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const float4 bb = *reinterpret_cast<const float4*>(bp + 8 * q);
-          st[4 * q] = bb.x; st[4 * q + 1] = bb.y; st[4 * q + 2] = bb.z; st[4 * q + 3] = bb.w;
-        }
-      }
+      f32x16 st = bias_acc(sB[buf] + 32 * vb + 4 * hh);
 #pragma unroll
       for (int s = 0; s < KS; ++s) st = mfma32(frag_kc(img, LD, 32 * vb, 16 * s), hb[s], st);
       float mx = st[0];
@@ -244,41 +214,24 @@ __global__ __launch_bounds__(256) void vocab_topk_combine_kernel(const float* __
 }
 
 // ---- host side --------------------------------------------------------------------------
-int vocab_topk_splits(int M, int V) {
-  // ≈ 2 workgroups per CU over (row blocks × vocab splits); every split ≥ 4 chunks (the rule of
-  // ce2_num_splits)
-  const int rb = (M + vtk::RB - 1) / vtk::RB, nchunks = (V + vtk::VC - 1) / vtk::VC;
-  int s = (512 + rb - 1) / rb;
-  s = s < 1 ? 1 : s;
-  const int cap = (nchunks + 3) / 4;
-  s = s > cap ? cap : s;
-  s = s > vtk::kMaxSplits ? vtk::kMaxSplits : s;
-  const int cps = (nchunks + s - 1) / s;
-  return (nchunks + cps - 1) / cps;
-}
+int vocab_topk_splits(int M, int V) { return vocab_splits(M, V, vtk::RB, vtk::VC, vtk::kMaxSplits); }
 int vocab_topk_kt(int k) { return k <= 1 ? 1 : (k <= 4 ? 4 : vtk::kMaxK); }
 
 template <int C, int KT>
-static void vocab_topk_run(const float* Hm, const int64_t* hidx, long long R, const uint16_t* W, const float* bias, int M,
-                           int V, int k, int nsplit, float* cand_v, int* cand_i, float2* part_ml, float* values,
-                           int64_t* indices, float* lse, hipStream_t st) {
-  const int nchunks = (V + vtk::VC - 1) / vtk::VC;
-  const int cps = (nchunks + nsplit - 1) / nsplit;
-  hipLaunchKernelGGL((vocab_topk_kernel<C, KT>), dim3((M + vtk::RB - 1) / vtk::RB, nsplit), dim3(256), 0, st, Hm, hidx, R,
-                     W, bias, M, V, cps, cand_v, cand_i, part_ml);
-  hipLaunchKernelGGL((vocab_topk_combine_kernel<KT>), dim3((M + 255) / 256), dim3(256), 0, st, cand_v, cand_i, part_ml,
-                     nsplit, M, V, k, values, indices, lse);
+static void vocab_topk_run(const VocabTopkArgs& a, hipStream_t st) {
+  const int nchunks = (a.V + vtk::VC - 1) / vtk::VC;
+  const int cps = (nchunks + a.nsplit - 1) / a.nsplit;
+  float2* part_ml = reinterpret_cast<float2*>(a.part_ml);
+  hipLaunchKernelGGL((vocab_topk_kernel<C, KT>), dim3((a.M + vtk::RB - 1) / vtk::RB, a.nsplit), dim3(256), 0, st, a.H,
+                     a.hidx, a.R, a.W, a.bias, a.M, a.V, cps, a.cand_v, a.cand_i, part_ml);
+  hipLaunchKernelGGL((vocab_topk_combine_kernel<KT>), dim3((a.M + 255) / 256), dim3(256), 0, st, a.cand_v, a.cand_i,
+                     part_ml, a.nsplit, a.M, a.V, a.k, a.values, a.indices, a.lse);
 }
 
-// C ∈ {64, 128}, 1 ≤ k ≤ 8, k ≤ V, M ≥ 1; cand_v / cand_i hold nsplit·M·vocab_topk_kt(k) entries
-void vocab_topk_launch(int C, const float* Hm, const int64_t* hidx, long long R, const uint16_t* W, const float* bias,
-                       int M, int V, int k, int nsplit, float* cand_v, int* cand_i, float2* part_ml, float* values,
-                       int64_t* indices, float* lse, hipStream_t st) {
-  const int kt = vocab_topk_kt(k);
-#define PIO_VTK(CC, KK)                                                                                          \
-  if (C == CC && kt == KK)                                                                                       \
-    return vocab_topk_run<CC, KK>(Hm, hidx, R, W, bias, M, V, k, nsplit, cand_v, cand_i, part_ml, values, indices, \
-                                  lse, st)
+void vocab_topk_launch(const VocabTopkArgs& a, hipStream_t st) {
+  const int kt = vocab_topk_kt(a.k);
+#define PIO_VTK(CC, KK) \
+  if (a.C == CC && kt == KK) return vocab_topk_run<CC, KK>(a, st)
   PIO_VTK(64, 1);
   PIO_VTK(64, 4);
   PIO_VTK(64, 8);

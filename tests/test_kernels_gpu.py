@@ -542,8 +542,11 @@ def test_ln_linear_bwd_dx_in_place_of_dres():
 
 # (1552, 2003) and (900, 3000): split counts that used to leave trailing vocab splits without
 # a chunk (an empty split read its rows' dH targets from LDS before any barrier)
+# (300, 256), (1000, 2) and (33, 3) at C = 64: a vocabulary of at most 256 entries (the two-pass
+# backward's one-hot-in-tile instance) with two, one and one partial vocabulary block, and 5, 32
+# and 2 appended dH grid rows
 @pytest.mark.parametrize("M,V,C", [(300, 1000, 64), (77, 10003, 64), (64, 257, 128), (1552, 2003, 64),
-                                   (900, 3000, 32)])
+                                   (900, 3000, 32), (300, 256, 64), (1000, 2, 64), (33, 3, 64)])
 def test_fused_cross_entropy(M, V, C):
     torch.manual_seed(5)
     h = bf(torch.randn(M, C, device=DEV))
@@ -592,6 +595,9 @@ def test_fused_cross_entropy(M, V, C):
     names = ("dH", "dW", "db", "dH rowmap", "dW acc", "db acc", "dW slab", "db slab")
     errs = {n: rel_fro(a, b) for a, b, n in zip(outs[0], outs[1], names)}
     assert all(e < 1e-2 for e in errs.values()), errs
+    if C == 64:  # the two-pass head has no backward without the forward's split partials
+        with pytest.raises(RuntimeError, match="needs u and u_ml"):
+            _ext().ce_bwd(hs2, lab, w, bias, s2, gout, cnt, torch.zeros(M, C, device=DEV), dW, db, False, None)
 
 
 def test_embed_mask_adamw():
