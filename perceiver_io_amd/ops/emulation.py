@@ -1441,7 +1441,7 @@ def sb_bwd(dz, x0, saved, params, scale, eps, pre=(), pre_saved=(), zero_out=Non
         o = (4 * L + (2 if pre else 0)) * C
         lns[:, o:o + C] = (dxn * xh).view(B, _SB_N, C).sum(1)
         lns[:, o + C:o + 2 * C] = dxn.view(B, _SB_N, C).sum(1)
-        dz = dres.float() + dxl
+        dz = dres.float() + dxl if dres is not None and dres.numel() else dxl  # (an empty dres: none)
         post_tail = [dqb.to(torch.bfloat16)]
 
     def per_sample(t):  # (B·32, C) → the sample sums (B, C)
