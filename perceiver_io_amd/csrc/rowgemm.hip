@@ -877,7 +877,12 @@ __device__ __forceinline__ void post_attn_bwd_body(
 #pragma unroll
   for (int j = 0; j < NCH; ++j) {
     const uint16_t* p = gr < R ? O + (long long)gr * C + rp_col(j) : reinterpret_cast<const uint16_t*>(kZero32B);
-    ob[j] = *reinterpret_cast<const bf16x8*>(p);
+    if constexpr (AV) {
+      ob[j] = *reinterpret_cast<const bf16x8*>(p);
+    } else {  // O rows only 2-byte aligned: no 16-byte load
+#pragma unroll
+      for (int e = 0; e < 8; ++e) ob[j][e] = (short)p[e];
+    }
   }
   const float mu = *(gr < R ? mean2 + gr : kZero32B), rs = *(gr < R ? rstd2 + gr : kZero32B);
   bf16x8 wr[NWB][NIW];
