@@ -1715,6 +1715,39 @@ std::vector<Tensor> text_mask(Tensor x, OptT pad, Tensor state, int64_t unk, int
   return {xm, lab};
 }
 
+// whole-word masking (text_mask_words_kernel): x (B, L); table: the vocabulary's bit-packed
+// continuation table, int32 (⌈hi / 32⌉,) on x's device — hi is the vocabulary size
+std::vector<Tensor> text_mask_words(Tensor x, OptT pad, Tensor state, Tensor table, int64_t unk, int64_t mask, double p,
+                                    int64_t lo, int64_t hi, bool advance) {
+  TORCH_CHECK(x.is_contiguous() && state.is_contiguous() && state.numel() == 3, "text_mask_words: bad x / state");
+  TORCH_CHECK(x.dim() == 2 && x.size(1) > 0, "text_mask_words: x must be (B, L)");
+  CHECK_CUDA(x);
+  CHECK_DT(x, torch::kInt64);
+  CHECK_DT(state, torch::kInt64);
+  CHECK_DT(table, torch::kInt32);
+  TORCH_CHECK(hi > lo && hi - lo < (1LL << 32), "text_mask_words: bad random-id range");
+  TORCH_CHECK(hi < (1LL << 31), "text_mask_words: vocabulary too large");
+  TORCH_CHECK(table.is_contiguous() && table.dim() == 1 && table.numel() == (hi + 31) / 32,
+              "text_mask_words: the continuation table must hold ceil(hi / 32) packed words");
+  TORCH_CHECK(table.device() == x.device() && state.device() == x.device(),
+              "text_mask_words: table and state must be on x's device");
+  const long long n = x.numel();
+  TORCH_CHECK(n < (1LL << 32), "text_mask_words: too many tokens");
+  TORCH_CHECK(x.size(1) < (1LL << 31), "text_mask_words: rows too long");
+  Tensor xm = torch::empty_like(x), lab = torch::empty_like(x);
+  const bool* pp = nullptr;
+  if (pad.has_value()) {
+    CHECK_DT(*pad, torch::kBool);
+    TORCH_CHECK(pad->is_contiguous() && pad->numel() == n && pad->device() == x.device(),
+                "text_mask_words: pad mask must match x");
+    pp = pad->data_ptr<bool>();
+  }
+  pio::text_mask_words_launch(x.data_ptr<int64_t>(), pp, state.data_ptr<int64_t>(), table.data_ptr<int32_t>(),
+                              xm.data_ptr<int64_t>(), lab.data_ptr<int64_t>(), n, (int)x.size(1), (int)hi, (int)unk,
+                              (int)mask, (float)p, (int)lo, (uint32_t)(hi - lo), advance ? 1 : 0, stream());
+  return {xm, lab};
+}
+
 // one launch per replayed step: dsts[i] <- srcs[i] (same device, dtype-agnostic byte copies of
 // contiguous tensors of equal size) and hyper_dst[:len(hyper)] <- hyper (values by kernel argument)
 // seed_dst + seeds: a captured step's dropout seed slots (int64, ≤ 64 values) written in the same launch
@@ -2655,6 +2688,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("job_offs") = std::vector<int64_t>());
   m.def("text_mask", &text_mask, py::arg("x"), py::arg("pad"), py::arg("state"), py::arg("unk"), py::arg("mask"),
         py::arg("p"), py::arg("lo"), py::arg("hi"), py::arg("advance") = true);
+  m.def("text_mask_words", &text_mask_words, py::arg("x"), py::arg("pad"), py::arg("state"), py::arg("table"),
+        py::arg("unk"), py::arg("mask"), py::arg("p"), py::arg("lo"), py::arg("hi"), py::arg("advance") = true);
   m.def("sumsq", &sumsq);
   m.def("adamw", &adamw, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("shadow"), py::arg("hyper"),
         py::arg("eps"), py::arg("wd"), py::arg("clip"), py::arg("gscale"), py::arg("l2") = false,

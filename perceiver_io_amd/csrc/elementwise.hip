@@ -192,6 +192,29 @@ __global__ __launch_bounds__(256) void embed_bwd_local_kernel(const int64_t* __r
 // fresh masks; every workgroup has read the counter before it takes its ticket.
 __device__ __forceinline__ float unit24(uint32_t h) { return (float)(h >> 8) * (1.0f / 16777216.0f); }
 
+// token i's outputs once its selection is known: the 80/10/10 split and the replacement id stay
+// keyed by the token's own index (both masking kernels)
+__device__ __forceinline__ void mask_token_out(int64_t* __restrict__ xm, int64_t* __restrict__ labels, long long i,
+                                               int64_t t, bool sel, uint32_t key, int mask_id, int lo, uint32_t range) {
+  const uint32_t ii = (uint32_t)i;
+  const bool msk = sel & (unit24(hash3(key, 1u, ii)) < 0.9f);
+  const bool rnd = msk & (unit24(hash3(key, 2u, ii)) < (1.0f / 9.0f));
+  const int64_t rid = (int64_t)lo + (int64_t)__umulhi(hash3(key, 3u, ii), range);
+  xm[i] = rnd ? rid : (msk ? (int64_t)mask_id : t);
+  labels[i] = sel ? t : (int64_t)-100;
+}
+// the last workgroup to finish bumps the counter and clears the ticket (block-uniform call)
+__device__ __forceinline__ void mask_advance(int64_t* __restrict__ state, int64_t ctr) {
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned* ticket = reinterpret_cast<unsigned*>(state + 2);
+    if (atomicAdd(ticket, 1u) == gridDim.x - 1) {
+      state[1] = ctr + 1;
+      *ticket = 0u;
+    }
+  }
+}
+
 __global__ void text_mask_kernel(const int64_t* __restrict__ x, const bool* __restrict__ pad, int64_t* __restrict__ state,
                                  int64_t* __restrict__ xm, int64_t* __restrict__ labels, long long n, int unk_id,
                                  int mask_id, float p, int lo, uint32_t range, int advance) {
@@ -199,26 +222,91 @@ __global__ void text_mask_kernel(const int64_t* __restrict__ x, const bool* __re
   const int64_t ctr = state[1];
   const uint32_t key = hash3((uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)ctr);
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const uint32_t ii = (uint32_t)i;
     const int64_t t = x[i];
     const bool special = (t == unk_id) | (pad != nullptr && pad[i]);
-    const bool sel = !special & (unit24(hash3(key, 0u, ii)) < p);
-    const bool msk = sel & (unit24(hash3(key, 1u, ii)) < 0.9f);
-    const bool rnd = msk & (unit24(hash3(key, 2u, ii)) < (1.0f / 9.0f));
-    const int64_t rid = (int64_t)lo + (int64_t)__umulhi(hash3(key, 3u, ii), range);
-    xm[i] = rnd ? rid : (msk ? (int64_t)mask_id : t);
-    labels[i] = sel ? t : (int64_t)-100;
+    const bool sel = !special & (unit24(hash3(key, 0u, (uint32_t)i)) < p);
+    mask_token_out(xm, labels, i, t, sel, key, mask_id, lo, range);
   }
-  if (advance) {
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      unsigned* ticket = reinterpret_cast<unsigned*>(state + 2);
-      if (atomicAdd(ticket, 1u) == gridDim.x - 1) {
-        state[1] = ctr + 1;
-        *ticket = 0u;
+  if (advance) mask_advance(state, ctr);
+}
+
+// Whole-word BERT masking: text_mask_kernel with the SELECTION hash keyed by the index of the
+// first token of the token's word, so a word is selected or left as a whole; the 80/10/10
+// split and the replacement id stay per token.  cont: the vocabulary's bit-packed continuation
+// table (WordPiece "##" pieces), V ids; an id outside [0, V) has bit 0 and is never an index.
+//   special(i) = x[i] == unk | pad[i]
+//   begin(i)   = col(i) == 0 | special(i) | special(i − 1) | !cont(x[i])
+//   head(i)    = the nearest j in i, i − 1, …, i − (kWordWindow − 1) with begin(j), else i
+//   sel(i)     = !special(i) & unit24(hash3(key, 0, head(i))) < p
+// A row's column 0 always begins a word, so the look-back over the flat index never leaves the
+// row.  The tail of a word longer than kWordWindow tokens finds no beginning in its window and
+// is masked token by token.
+// One thread per token, 256-token tiles in a block-uniform grid-stride loop.  Per tile every
+// wave ballots two bits per token — s = special and b = col == 0 | special | !cont — into LDS
+// (wave 0 also those of the kWordWindow tokens before the tile, the halo), so begin = b |
+// (s shifted up one token) and head come from two 16-bit windows of the tile's bit image: no
+// dependent global loads.  The bit image is double-buffered by tile parity: one barrier a tile.
+static_assert(kWordWindow == 16, "the look-back window is read as 16 bits of the tile's bit image");
+__global__ __launch_bounds__(256) void text_mask_words_kernel(
+    const int64_t* __restrict__ x, const bool* __restrict__ pad, int64_t* __restrict__ state,
+    const int32_t* __restrict__ cont, int64_t* __restrict__ xm, int64_t* __restrict__ labels, long long n, int L, int V,
+    int unk_id, int mask_id, float p, int lo, uint32_t range, int advance) {
+  // word 0: the halo in its top 16 bits (tokens base − 16 … base − 1), words 1–4: the tile's waves
+  __shared__ unsigned long long sB[2][5], sS[2][5];
+  const uint64_t seed = (uint64_t)state[0];
+  const int64_t ctr = state[1];
+  const uint32_t key = hash3((uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)ctr);
+  const int tid = threadIdx.x, w = wave_id();
+  const long long ntiles = (n + 255) / 256;
+  int buf = 0;
+  for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x, buf ^= 1) {
+    const long long base = tile * 256, i = base + tid;
+    // this token's two bits
+    const bool in = i < n;
+    const int64_t t = in ? x[i] : 0;
+    const bool s = in && ((t == unk_id) | (pad != nullptr && pad[i]));
+    const bool tin = t >= 0 && t < V;
+#if PIO_CHECKS
+    if (in && !tin) pio_flag(kErrEmbedId);
+#endif
+    const bool c = in && tin && ((cont[tin ? t >> 5 : 0] >> (t & 31)) & 1);
+    const bool b = in && (((uint32_t)i % (uint32_t)L == 0u) | s | !c);  // n < 2^32
+    const unsigned long long mb = __ballot(b), ms = __ballot(s);
+    if (lane_id() == 0) {
+      sB[buf][1 + w] = mb;
+      sS[buf][1 + w] = ms;
+    }
+    if (w == 0) {  // halo: lanes 0–15 of wave 0 take tokens base − 16 … base − 1 (none before token 0)
+      const long long j = base - kWordWindow + tid;
+      const bool hin = tid < kWordWindow && j >= 0;
+      const int64_t ht = hin ? x[j] : 0;
+      const bool hs = hin && ((ht == unk_id) | (pad != nullptr && pad[j]));
+      const bool htin = ht >= 0 && ht < V;
+      const bool hc = hin && htin && ((cont[htin ? ht >> 5 : 0] >> (ht & 31)) & 1);
+      const bool hb = hin && (((uint32_t)j % (uint32_t)L == 0u) | hs | !hc);
+      const unsigned long long hmb = __ballot(hb), hms = __ballot(hs);
+      if (tid == 0) {
+        sB[buf][0] = hmb << 48;
+        sS[buf][0] = hms << 48;
       }
     }
+    __syncthreads();
+    if (in) {
+      // bit 64 + k of the image is tile token k.  begin bits of tokens i − 15 … i: image bits from
+      // q = 49 + tid; the special bits of their predecessors: from q − 1
+      const int q = 64 - (kWordWindow - 1) + tid, q1 = q - 1;
+      const int wq = q >> 6, sq = q & 63, wq1 = q1 >> 6, sq1 = q1 & 63;
+      unsigned long long vb = sB[buf][wq] >> sq, vs = sS[buf][wq1] >> sq1;
+      // a window that runs into the next word (never past word 4: q ≤ 304 = 4·64 + 48)
+      if (sq > 64 - kWordWindow) vb |= sB[buf][wq + 1] << (64 - sq);
+      if (sq1 > 64 - kWordWindow) vs |= sS[buf][wq1 + 1] << (64 - sq1);
+      const uint32_t beg = (uint32_t)(vb | vs) & 0xFFFFu;  // bit 15: token i, bit 0: token i − 15
+      const uint32_t back = beg ? (uint32_t)__clz((int)beg) - 16u : 0u;
+      const bool sel = !s & (unit24(hash3(key, 0u, (uint32_t)i - back)) < p);
+      mask_token_out(xm, labels, i, t, sel, key, mask_id, lo, range);
+    }
   }
+  if (advance) mask_advance(state, ctr);
 }
 
 __global__ void cast_bf16_kernel(const float* __restrict__ x, uint16_t* __restrict__ y, long long n) {
@@ -271,6 +359,12 @@ void text_mask_launch(const int64_t* x, const bool* pad, int64_t* state, int64_t
                       int unk_id, int mask_id, float p, int lo, uint32_t range, int advance, hipStream_t st) {
   hipLaunchKernelGGL(text_mask_kernel, grid_for(n), dim3(256), 0, st, x, pad, state, xm, labels, n, unk_id, mask_id, p, lo,
                      range, advance);
+}
+void text_mask_words_launch(const int64_t* x, const bool* pad, int64_t* state, const int32_t* cont, int64_t* xm,
+                            int64_t* labels, long long n, int L, int V, int unk_id, int mask_id, float p, int lo,
+                            uint32_t range, int advance, hipStream_t st) {
+  hipLaunchKernelGGL(text_mask_words_kernel, grid_for(n), dim3(256), 0, st, x, pad, state, cont, xm, labels, n, L, V,
+                     unk_id, mask_id, p, lo, range, advance);
 }
 // dst[idx[r]][:] += src[r][:] — the backward of a row gather (rows of idx may repeat: fp32
 // atomics; an index outside dst is skipped).  One thread per 4 columns.

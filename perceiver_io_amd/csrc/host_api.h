@@ -436,6 +436,13 @@ void embed_bwd_sorted_launch(const int64_t* sorted_ids, const int64_t* perm, con
                              int C, float scale, hipStream_t st);
 void text_mask_launch(const int64_t* x, const bool* pad, int64_t* state, int64_t* xm, int64_t* labels, long long n,
                       int unk_id, int mask_id, float p, int lo, uint32_t range, int advance, hipStream_t st);
+// whole-word masking looks for a word's first token among this many positions (the token's own
+// included); ops/emulation.py WORD_WINDOW is the same number
+constexpr int kWordWindow = 16;
+// x: (n / L, L) rows; cont: bit-packed continuation table over V ids, ⌈V / 32⌉ words
+void text_mask_words_launch(const int64_t* x, const bool* pad, int64_t* state, const int32_t* cont, int64_t* xm,
+                            int64_t* labels, long long n, int L, int V, int unk_id, int mask_id, float p, int lo,
+                            uint32_t range, int advance, hipStream_t st);
 void index_add_rows_launch(float* dst, long long nrows, const int64_t* idx, const float* src, long long R, int C,
                            hipStream_t st);
 void gather_rows_launch(float* out, const float* src, long long nrows, const int64_t* idx, long long R, int C,

@@ -32,7 +32,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..parallel.reducer import bucket_ready_point, ready_point_armed
-from ..utils.tokenizer import MASK_TOKEN, SPECIAL_TOKENS, UNK_TOKEN
+from ..utils.tokenizer import MASK_TOKEN, SPECIAL_TOKENS, UNK_TOKEN, continuation_table, pack_bits
 from .adapters import InputAdapter, OutputAdapter
 from .blocks import Sequential, cross_attention_layer, init_latent_, self_attention_block
 
@@ -237,19 +237,44 @@ class PerceiverIO(Sequential):
 class TextMasking(nn.Module):
     """BERT masking: of the non-special tokens (not UNK, not PAD) select 15 %; of those
     80 % → ``[MASK]``, 10 % → random non-special id, 10 % unchanged.  Labels are the
-    original ids at selected positions and -100 elsewhere."""
+    original ids at selected positions and -100 elsewhere.
+
+    ``whole_word=True`` selects whole words: the tokens of a word (a WordPiece piece and the
+    continuation pieces after it, ``continuation`` being the bool ``(vocab_size,)`` table of
+    ``utils.tokenizer.continuation_table``) are selected together, every non-special token still
+    with probability ``mask_p`` and its own 80/10/10 draw.  Special tokens are words of their own
+    and end the word before them; a word never crosses a row; of a word longer than 16 tokens only
+    the first 16 go together, the rest token by token.  ``word_clump`` (Σ len² / Σ len over the
+    words of typical batches, ``utils.tokenizer.word_clump``) widens the loss's fixed selection
+    capacity for the correlated counts; it is 1.0 without ``whole_word``."""
 
     def __init__(self, vocab_size: int, unk_token_id: int = 1, mask_token_id: int = 2,
-                 num_special_tokens: int = len(SPECIAL_TOKENS), mask_p: float = 0.15):
+                 num_special_tokens: int = len(SPECIAL_TOKENS), mask_p: float = 0.15, whole_word: bool = False,
+                 continuation: Optional[torch.Tensor] = None, word_clump: float = 1.0):
         super().__init__()
         self.vocab_size = vocab_size
         self.unk_token_id = unk_token_id
         self.mask_token_id = mask_token_id
         self.num_special_tokens = num_special_tokens
         self.mask_p = mask_p
+        self.whole_word = bool(whole_word)
+        self.word_clump = float(word_clump) if self.whole_word else 1.0
+        table = None
+        if self.whole_word:
+            if continuation is None:
+                raise ValueError("whole_word=True needs the vocabulary's continuation table (utils.tokenizer."
+                                 "continuation_table, or TextMasking.create(tokenizer, whole_word=True))")
+            if continuation.dim() != 1 or continuation.numel() != vocab_size:
+                raise ValueError(f"the continuation table has {continuation.numel()} entries, "
+                                 f"the vocabulary {vocab_size}")
+            table = pack_bits(continuation.to(torch.bool))
+        # derived from the tokenizer, not trained: not part of the state dict
+        self.register_buffer("word_table", table, persistent=False)
 
     @staticmethod
     def create(tokenizer, **kwargs):
+        if kwargs.get("whole_word") and kwargs.get("continuation") is None:
+            kwargs["continuation"] = continuation_table(tokenizer)
         return TextMasking(vocab_size=tokenizer.get_vocab_size(),
                            unk_token_id=tokenizer.token_to_id(UNK_TOKEN),
                            mask_token_id=tokenizer.token_to_id(MASK_TOKEN),
@@ -257,9 +282,13 @@ class TextMasking(nn.Module):
 
     def forward(self, x, pad_mask=None, generator: Optional[torch.Generator] = None):
         if ops.get_backend() == "reference":
+            if self.whole_word:
+                raise RuntimeError("the reference backend has no whole-word masking (the reference masks token "
+                                   "by token): use another backend or whole_word=False")
             return self._reference_masking(x, pad_mask)
         return ops.masking.text_masking(x, pad_mask, self.vocab_size, self.unk_token_id, self.mask_token_id,
-                                        self.num_special_tokens, self.mask_p, generator=generator)
+                                        self.num_special_tokens, self.mask_p, generator=generator,
+                                        word_table=self.word_table if self.whole_word else None)
 
     def _reference_masking(self, x, pad_mask):
         """The reference's compute pattern (boolean-index scatter, ``randint(size=sum)`` —
@@ -349,6 +378,7 @@ class PerceiverMLM(nn.Module):
                            if ops.use_hip(x_masked) else None)
         try:
             x_latent, _ = self.encoder(x_masked, pad_mask)
-            return ops.mlm_head.masked_decode_loss(self.decoder, x_latent, labels, p=self.masking.mask_p)
+            return ops.mlm_head.masked_decode_loss(self.decoder, x_latent, labels, p=self.masking.mask_p,
+                                                   clump=self.masking.word_clump)
         finally:
             look["want_kv"] = look["have_q"] = None

@@ -929,8 +929,31 @@ def _mulhi32(a, b: int):
     return ((a >> 16) * b + (((a & 0xFFFF) * b) >> 16)) >> 16
 
 
-def text_mask(x, pad, state, unk, mask, p, lo, hi, advance=True):
-    """Counter-hash BERT masking, bit-exact with ``text_mask_kernel`` (elementwise.hip)."""
+WORD_WINDOW = 16  # csrc/host_api.h kWordWindow
+
+
+def word_heads(special, cont):
+    """Flat index ``(B, L)`` of the first token of every token's word (``text_mask_words_kernel``):
+    a token begins a word at column 0, when it or its predecessor is special, or when its id is no
+    continuation piece; the head is the nearest beginning among the token and the
+    ``WORD_WINDOW - 1`` before it, the token itself if there is none (the tail of a longer word)."""
+    B, L = special.shape
+    begin = special | ~cont
+    begin[:, 0] = True
+    begin[:, 1:] |= special[:, :-1]
+    idx = torch.arange(B * L, device=special.device, dtype=torch.int64).view(B, L)
+    head, found = idx.clone(), begin.clone()
+    for k in range(1, min(WORD_WINDOW, L)):
+        take = torch.zeros_like(found)
+        take[:, k:] = begin[:, :-k] & ~found[:, k:]
+        head = torch.where(take, idx - k, head)
+        found = found | take
+    return head
+
+
+def text_mask(x, pad, state, unk, mask, p, lo, hi, advance=True, _head=None):
+    """Counter-hash BERT masking, bit-exact with ``text_mask_kernel`` (elementwise.hip).
+    ``_head``: the index that keys the selection hash (``text_mask_words``), default the token's."""
     seed = int(state[0].item()) & 0xFFFFFFFFFFFFFFFF
     ctr = int(state[1].item())
     key = hash3(torch.tensor(seed & M32), torch.tensor(seed >> 32), torch.tensor(ctr & M32))
@@ -939,6 +962,8 @@ def text_mask(x, pad, state, unk, mask, p, lo, hi, advance=True):
     special = x == unk
     if pad is not None:
         special = special | pad
+    if _head is not None:
+        h[0] = hash3(key.to(x.device), torch.tensor(0, device=x.device), _head(special))
     sel = ~special & (_unit24(h[0]) < p)
     msk = sel & (_unit24(h[1]) < 0.9)
     rnd = msk & (_unit24(h[2]) < 1.0 / 9.0)
@@ -947,6 +972,25 @@ def text_mask(x, pad, state, unk, mask, p, lo, hi, advance=True):
     if advance:
         state[1] += 1
     return xm, torch.where(sel, x, torch.full_like(x, -100))
+
+
+def unpack_bits(table, ids, size: int):
+    """Bit ``ids`` of the bit-packed int32 ``table`` over ``size`` entries (bool, shape of ``ids``);
+    an id outside ``[0, size)`` reads as 0 and is never used as an index."""
+    ok = (ids >= 0) & (ids < size)
+    t = torch.where(ok, ids, torch.zeros_like(ids))
+    return ok & (((table.to(torch.int64)[t >> 5] >> (t & 31)) & 1) != 0)
+
+
+def text_mask_words(x, pad, state, table, unk, mask, p, lo, hi, advance=True):
+    """Whole-word masking, bit-exact with ``text_mask_words_kernel`` (elementwise.hip):
+    ``text_mask`` with the selection hash keyed by the first token of the token's word
+    (:func:`word_heads`).  ``x`` is ``(B, L)``; ``table`` the bit-packed int32 continuation table of
+    the ``hi`` vocabulary ids."""
+    if x.dim() != 2 or table.dtype != torch.int32 or table.numel() != (hi + 31) // 32:
+        raise ValueError("text_mask_words: x must be (B, L) and table int32 with ceil(hi / 32) words")
+    cont = unpack_bits(table, x, hi)
+    return text_mask(x, pad, state, unk, mask, p, lo, hi, advance, _head=lambda special: word_heads(special, cont))
 
 
 def sumsq(g, part):

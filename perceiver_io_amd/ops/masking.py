@@ -9,7 +9,9 @@ drawn once from torch's default generator (``torch.manual_seed`` makes runs repr
 An explicit ``generator`` draws a one-off seed from it instead (counter 0, state untouched).
 
 The CPU path evaluates the same hash (``ops/emulation.py``), so both backends produce
-identical masks from the same state.  Unlike the reference, the input ids are never modified
+identical masks from the same state.  With a continuation table the selection draw is keyed by
+the index of the first token of the token's word (whole-word masking); the table of all zeros
+reproduces the per-token masks bit for bit.  Unlike the reference, the input ids are never modified
 in place (defect D4).
 """
 from __future__ import annotations
@@ -49,7 +51,10 @@ def reset_mask_state(seed: Optional[int] = None):
 
 def text_masking(x: torch.Tensor, pad_mask: Optional[torch.Tensor], vocab_size: int, unk_token_id: int,
                  mask_token_id: int, num_special_tokens: int, mask_p: float = 0.15,
-                 generator: Optional[torch.Generator] = None):
+                 generator: Optional[torch.Generator] = None, word_table: Optional[torch.Tensor] = None):
+    """``word_table``: the vocabulary's bit-packed continuation table (``utils.tokenizer.pack_bits``
+    of ``continuation_table``) selects whole words (``text_mask_words_kernel``): all tokens of a
+    word are selected together, each still with its own 80/10/10 draw.  ``None``: per token."""
     from . import use_hip
 
     if generator is not None:  # one-off seed from the caller's generator
@@ -59,5 +64,10 @@ def text_masking(x: torch.Tensor, pad_mask: Optional[torch.Tensor], vocab_size: 
         state, advance = mask_state(x.device), True
     pm = pad_mask.to(torch.bool).contiguous() if pad_mask is not None else None
     K = ext.require() if use_hip(x) else emulation
+    if word_table is not None:
+        if x.dim() != 2:
+            raise ValueError("whole-word masking needs (B, L) token ids")
+        return K.text_mask_words(x.contiguous(), pm, state, word_table, unk_token_id, mask_token_id, mask_p,
+                                 num_special_tokens, vocab_size, advance)
     return K.text_mask(x.contiguous(), pm, state, unk_token_id, mask_token_id, mask_p, num_special_tokens, vocab_size,
                        advance)

@@ -60,10 +60,13 @@ def check_overflow(reset: bool = False) -> bool:
     return False
 
 
-def capacity(n_positions: int, p: float = 0.15) -> int:
+def capacity(n_positions: int, p: float = 0.15, clump: float = 1.0) -> int:
+    """Slots for the selected positions of a batch: expected + 8σ + 64.  ``clump``: the variance
+    inflation of whole-word selection (``utils.tokenizer.word_clump``: Σ len² / Σ len over the
+    words), σ² = μ(1 − p)·clump; 1.0 is independent tokens."""
     p = min(max(float(p), 1e-6), 1.0)
     mu = n_positions * p
-    cap = int(math.ceil(mu + 8.0 * math.sqrt(max(mu * (1 - p), 1.0)) + 64))
+    cap = int(math.ceil(mu + 8.0 * math.sqrt(max(mu * (1 - p) * max(float(clump), 1.0), 1.0)) + 64))
     return max(1, min(n_positions, cap))
 
 
@@ -172,12 +175,13 @@ def masked_lm_loss(h: torch.Tensor, labels: torch.Tensor, weight: torch.Tensor, 
 # ------------------------------------------------------------------------------------------
 # training-time decode of the selected positions only
 # ------------------------------------------------------------------------------------------
-def row_capacity(length: int, p: float = 0.15) -> int:
+def row_capacity(length: int, p: float = 0.15, clump: float = 1.0) -> int:
     """Per-sequence slots for selected positions: expected + 8σ + 16, a multiple of 32, ≤ L
-    (L = 512, p = 0.15: 160 slots for ~77 selected; overflow probability < 1e-15 per sequence)."""
+    (L = 512, p = 0.15: 160 slots for ~77 selected; overflow probability < 1e-15 per sequence).
+    ``clump``: as in :func:`capacity` (σ² = μ(1 − p)·clump)."""
     p = min(max(float(p), 1e-6), 1.0)
     mu = length * p
-    cap = int(math.ceil(mu + 8.0 * math.sqrt(max(mu * (1 - p), 1.0)) + 16))
+    cap = int(math.ceil(mu + 8.0 * math.sqrt(max(mu * (1 - p) * max(float(clump), 1.0), 1.0)) + 16))
     cap = (cap + 31) // 32 * 32
     return max(1, min(length, cap))
 
@@ -203,14 +207,14 @@ def compact_per_row(labels: torch.Tensor, cap: int):
 
 
 def compact_lm_loss(h: torch.Tensor, labels_c: torch.Tensor, count: torch.Tensor, weight: torch.Tensor,
-                    bias: torch.Tensor, positions: int, p: float = 0.15):
+                    bias: torch.Tensor, positions: int, p: float = 0.15, clump: float = 1.0):
     """Mean CE over the rows of a per-sequence-compacted ``(B, cap, C)`` batch whose label is
     not -100.  The HIP path compacts those rows once more over the whole batch (capacity for
     ``positions`` tokens at the masking rate), so the vocab GEMMs see only real rows."""
     from . import use_hip
 
     if use_hip(h) and h.shape[-1] in (32, 64, 128):
-        idx, lab, cnt = compact_rows(labels_c, capacity(positions, p))
+        idx, lab, cnt = compact_rows(labels_c, capacity(positions, p, clump))
         return _MaskedCE.apply(h, weight, bias, idx, lab, cnt)
     lab = labels_c.reshape(-1)
     logits = F.linear(h.reshape(-1, h.shape[-1]), weight, bias)
@@ -325,7 +329,7 @@ class _SelectQueries(torch.autograd.Function):
         return None, None, None, None, None
 
 
-def masked_decode_loss(decoder, x_latent: torch.Tensor, labels: torch.Tensor, p: float = 0.15):
+def masked_decode_loss(decoder, x_latent: torch.Tensor, labels: torch.Tensor, p: float = 0.15, clump: float = 1.0):
     """MLM loss decoding only the selected positions.
 
     Decoder queries never interact (reference ``perceiver/model.py:236``: one cross-attention
@@ -333,7 +337,8 @@ def masked_decode_loss(decoder, x_latent: torch.Tensor, labels: torch.Tensor, p:
     sequence — gathered into ``row_capacity(L, p)`` slots — gives the same loss and gradients as
     decoding all ``L`` at a third of the decoder cost.  The output-query
     gradient flows back through the gather (index_select → index_add).  ``p`` is the masking
-    rate (``TextMasking.mask_p``): it sizes both capacities.
+    rate (``TextMasking.mask_p``) and ``clump`` the variance inflation of whole-word selection
+    (``TextMasking.word_clump``): they size both capacities.
     """
     from ..parallel.reducer import bucket_ready_point
     from . import use_hip
@@ -342,10 +347,10 @@ def masked_decode_loss(decoder, x_latent: torch.Tensor, labels: torch.Tensor, p:
     B, L = labels.shape
     decoder.check_latent(x_latent)
     lin = decoder.output_adapter.linear
-    cap = row_capacity(L, p)
+    cap = row_capacity(L, p, clump)
     if use_hip(x_latent) and lin.weight.shape[1] in (32, 64, 128):
         # the kernel ORs the overflow into the persistent per-device flag itself
-        q, idx, gidx, glab, total, ovf = _SelectQueries.apply(decoder.output, labels, cap, capacity(B * L, p),
+        q, idx, gidx, glab, total, ovf = _SelectQueries.apply(decoder.output, labels, cap, capacity(B * L, p, clump),
                                                               overflow_flag(labels.device).view(1))
         global _overflow
         _overflow = ovf
@@ -354,7 +359,7 @@ def masked_decode_loss(decoder, x_latent: torch.Tensor, labels: torch.Tensor, p:
     idx, labels_c, count = compact_per_row(labels, cap)
     q = _GatherQueries.apply(decoder.output, idx.reshape(-1)).view(B, cap, -1)
     h = decoder.cross_attention(q, x_latent)
-    return compact_lm_loss(h, labels_c, count, lin.weight, lin.bias, B * L, p)
+    return compact_lm_loss(h, labels_c, count, lin.weight, lin.bias, B * L, p, clump)
 
 
 def classification_loss(decoder, x_latent: torch.Tensor, labels: torch.Tensor):

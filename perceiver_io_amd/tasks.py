@@ -400,7 +400,13 @@ def _stale_ckpt_overrides(clf_ckpt: str) -> dict:
 
 class LitMaskedLanguageModel(LitModel):
     def __init__(self, vocab_size: int, max_seq_len: int, *args: Any, masked_samples: Optional[List[str]] = None,
-                 num_predictions: int = 3, **kwargs: Any):
+                 num_predictions: int = 3, whole_word_masking: bool = False, mask_p: float = 0.15,
+                 word_clump: float = 2.0, tokenizer_path: Optional[str] = None, **kwargs: Any):
+        """``whole_word_masking``: select whole words (``TextMasking(whole_word=True)``) with the
+        continuation table of the WordPiece tokenizer at ``tokenizer_path`` (default: the packaged
+        tokenizer of ``vocab_size``); ``word_clump`` then sizes the loss's selection capacity (Σ len² /
+        Σ len over the words of the corpus, ``utils.tokenizer.word_clump``; unused otherwise).
+        ``mask_p``: the masking rate.  Checkpoints from before these options load with the defaults."""
         super().__init__(*args, **kwargs)
         self.model = self.create_model()
         self.loss = nn.CrossEntropyLoss()
@@ -423,9 +429,29 @@ class LitMaskedLanguageModel(LitModel):
                                            num_output_channels=hp.num_latent_channels)
         decoder = PerceiverDecoder(output_adapter=output_adapter, latent_shape=self.latent_shape,
                                    num_cross_attention_heads=hp.num_decoder_cross_attention_heads, dropout=hp.dropout)
+        whole_word = bool(hp.get("whole_word_masking", False))
         masking = TextMasking(hp.vocab_size, unk_token_id=UNK_TOKEN_ID, mask_token_id=MASK_TOKEN_ID,
-                              num_special_tokens=len(SPECIAL_TOKENS))
+                              num_special_tokens=len(SPECIAL_TOKENS), mask_p=hp.get("mask_p", 0.15),
+                              whole_word=whole_word, continuation=self._continuation() if whole_word else None,
+                              word_clump=hp.get("word_clump", 2.0))
         return PerceiverMLM(encoder, decoder, masking)
+
+    def _continuation(self):
+        """The continuation table of ``tokenizer_path`` (default: the packaged tokenizer of the
+        vocabulary size, the file the data module installs)."""
+        from .data.imdb import shipped_tokenizer
+        from .utils.tokenizer import continuation_table
+
+        hp = self.hparams
+        path = hp.get("tokenizer_path") or shipped_tokenizer(hp.vocab_size)
+        if not os.path.exists(path):
+            raise FileNotFoundError(f"whole_word_masking needs the tokenizer JSON: {path} does not exist "
+                                    "(pass tokenizer_path=, the file the data was tokenized with)")
+        table = continuation_table(path)
+        if table.numel() != hp.vocab_size:
+            raise ValueError(f"{path} has {table.numel()} tokens, vocab_size is {hp.vocab_size}: whole-word masking "
+                             "needs the tokenizer of the model's vocabulary")
+        return table
 
     def forward(self, batch):
         _, x, x_mask = batch
