@@ -1903,6 +1903,67 @@ void pixel_ce_bwd(Tensor h, Tensor w, Tensor b, Tensor labels, Tensor wts, Tenso
                            db.data_ptr<float>(), stream());
 }
 
+namespace {
+void check_seg_loss(const Tensor& h, const Tensor& w, const Tensor& b, const Tensor& labels, const Tensor& wts,
+                    double gamma, double ce_weight, double dice_weight, double eps) {
+  check_pixel_head(h, w, b, labels, wts);
+  CHECK_CUDA(h);
+  TORCH_CHECK(w.get_device() == h.get_device() && b.get_device() == h.get_device() &&
+                  labels.get_device() == h.get_device() && wts.get_device() == h.get_device(),
+              "pixel seg: every operand on h's device");
+  // written so that a NaN fails each rule
+  TORCH_CHECK(gamma >= 0.0 && std::isfinite(gamma), "pixel seg: focal gamma must be >= 0, got ", gamma);
+  TORCH_CHECK(ce_weight >= 0.0 && dice_weight >= 0.0 && std::isfinite(ce_weight) && std::isfinite(dice_weight) &&
+                  ce_weight + dice_weight > 0.0,
+              "pixel seg: ce_weight and dice_weight must be >= 0 and not both 0, got ", ce_weight, ", ", dice_weight);
+  TORCH_CHECK(eps > 0.0 && std::isfinite(eps), "pixel seg: dice eps must be > 0, got ", eps);
+}
+}  // namespace
+
+// Focal cross-entropy + soft Dice of the head (pixel_head.hip pixel_seg_*; the definition is there) →
+// [stats (4 + 5K sums: the 4 + 2K of pixel_ce_fwd with Σ w·q^γ·ce first, then I_c, P_c, T_c | acc,
+//  acc_1 … acc_{K-1} | F, D | the K per-class soft Dice coefficients), loss (0-dim)]
+std::vector<Tensor> pixel_seg_fwd(Tensor h, Tensor w, Tensor b, Tensor labels, Tensor wts, double gamma,
+                                  double ce_weight, double dice_weight, double eps) {
+  check_seg_loss(h, w, b, labels, wts, gamma, ce_weight, dice_weight, eps);
+  const long long R = h.size(0);
+  const int K = (int)w.size(0);
+  // every block of the launch stores its whole partial row (zeros only for an empty input)
+  Tensor part = R > 0 ? torch::empty({pio::pixel_ce_blocks(R), 4 + 5 * K}, h.options())
+                      : torch::zeros({pio::pixel_ce_blocks(R), 4 + 5 * K}, h.options());
+  Tensor stats = torch::empty({6 + 7 * K}, h.options()), loss = torch::empty({}, h.options());
+  pio::pixel_seg_fwd_launch((int)h.size(1), K, f32p(h), f32p(w), f32p(b), labels.data_ptr<int64_t>(), f32p(wts),
+                            (float)gamma, (float)ce_weight, (float)dice_weight, (float)eps, R, part.data_ptr<float>(),
+                            stats.data_ptr<float>(), loss.data_ptr<float>(), stream());
+  return {stats, loss};
+}
+
+// dH (R, C) written; dW (K, C) / db (K) += the head's weight gradients (fixed-order sums); stats is
+// pixel_seg_fwd's, computed with the same parameters
+void pixel_seg_bwd(Tensor h, Tensor w, Tensor b, Tensor labels, Tensor wts, double gamma, double ce_weight,
+                   double dice_weight, double eps, Tensor gout, Tensor stats, Tensor dH, Tensor dW, Tensor db) {
+  check_seg_loss(h, w, b, labels, wts, gamma, ce_weight, dice_weight, eps);
+  CHECK_DT(gout, torch::kFloat32); CHECK_DT(stats, torch::kFloat32); CHECK_DT(dH, torch::kFloat32);
+  CHECK_DT(dW, torch::kFloat32); CHECK_DT(db, torch::kFloat32);
+  const long long R = h.size(0);
+  const int K = (int)w.size(0), C = (int)h.size(1);
+  TORCH_CHECK(dH.is_contiguous() && dH.sizes() == h.sizes() && gout.numel() == 1 && stats.is_contiguous() &&
+                  stats.numel() >= 4 + 5 * K,
+              "pixel seg bwd: dH like h, scalar loss gradient, the forward's stats");
+  TORCH_CHECK(dW.is_contiguous() && dW.numel() == w.numel() && db.is_contiguous() && db.numel() == b.numel(),
+              "pixel seg bwd: dW / db like w / b");
+  TORCH_CHECK(gout.get_device() == h.get_device() && stats.get_device() == h.get_device() &&
+                  dH.get_device() == h.get_device() && dW.get_device() == h.get_device() &&
+                  db.get_device() == h.get_device(),
+              "pixel seg bwd: every operand on h's device");
+  Tensor part = R > 0 ? torch::empty({pio::pixel_ce_blocks(R), (int64_t)K * C + K}, h.options())
+                      : torch::zeros({pio::pixel_ce_blocks(R), (int64_t)K * C + K}, h.options());
+  pio::pixel_seg_bwd_launch(C, K, f32p(h), f32p(w), f32p(b), labels.data_ptr<int64_t>(), f32p(wts), (float)gamma,
+                            (float)ce_weight, (float)dice_weight, (float)eps, f32p(gout), f32p(stats), R,
+                            dH.data_ptr<float>(), part.data_ptr<float>(), dW.data_ptr<float>(), db.data_ptr<float>(),
+                            stream());
+}
+
 // Inference head (pixel_head.hip pixel_predict_kernel): h (R = B·Q, C), one row per query pixel →
 // [classes (R) uint8, conf (R) fp32, class_map (B, npix) uint8, confusion partials
 // (blocks, K·K) int32 — only with labels].  class_map is cleared on the stream before the launch;
@@ -2658,6 +2719,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("batch_sum2", &batch_sum2, py::arg("a"), py::arg("b"), py::arg("ob_acc") = py::none());
   m.def("pixel_ce_fwd", &pixel_ce_fwd);
   m.def("pixel_ce_bwd", &pixel_ce_bwd);
+  m.def("pixel_seg_fwd", &pixel_seg_fwd);
+  m.def("pixel_seg_bwd", &pixel_seg_bwd);
   m.def("pixel_predict", &pixel_predict, py::arg("h"), py::arg("w"), py::arg("b"), py::arg("qidx"), py::arg("qvalid"),
         py::arg("Q"), py::arg("npix"), py::arg("labels") = py::none());
   m.def("nonzero_compact", &nonzero_compact, py::arg("img"), py::arg("cap"), py::arg("segs") = 0, py::arg("tile") = 0);

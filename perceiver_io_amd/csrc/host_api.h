@@ -568,6 +568,15 @@ void pixel_ce_fwd_launch(int C, int K, const float* H, const float* W, const flo
 void pixel_ce_bwd_launch(int C, int K, const float* H, const float* W, const float* bias, const int64_t* labels,
                          const float* wts, const float* gout, const float* stats, long long R, float* dH, float* part,
                          float* dW, float* db, hipStream_t st);
+// focal cross-entropy + soft Dice on the same row pass.  part: (pixel_ce_blocks(R), 4 + 5K) forward,
+// (pixel_ce_blocks(R), K·C + K) backward, zero-filled by the caller when R == 0; stats: 6 + 7K floats
+void pixel_seg_fwd_launch(int C, int K, const float* H, const float* W, const float* bias, const int64_t* labels,
+                          const float* wts, float gamma, float ce_weight, float dice_weight, float eps, long long R,
+                          float* part, float* stats, float* loss, hipStream_t st);
+void pixel_seg_bwd_launch(int C, int K, const float* H, const float* W, const float* bias, const int64_t* labels,
+                          const float* wts, float gamma, float ce_weight, float dice_weight, float eps,
+                          const float* gout, const float* stats, long long R, float* dH, float* part, float* dW,
+                          float* db, hipStream_t st);
 // cpart: (pixel_ce_blocks(R), K·K) int32 when labels are given, else nullptr; cmap (R / Q, npix) is
 // zero-filled by the caller before this launch
 void pixel_predict_launch(int C, int K, const float* H, const float* W, const float* bias, const int64_t* qidx,

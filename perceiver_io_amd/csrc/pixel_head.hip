@@ -373,6 +373,305 @@ void pixel_predict_launch(int C, int K, const float* H, const float* W, const fl
                           uint8_t* classes, float* conf, uint8_t* cmap, int* cpart, hipStream_t st) {
   if (R > 0) PH_DISPATCH(pixel_predict_kernel, H, W, bias, qidx, qvalid, labels, R, Q, npix, classes, conf, cmap, cpart);
 }
+
+// ---- segmentation loss: focal cross-entropy + soft Dice on the same row pass -------------------
+// With p = softmax(z), pt = p[lab], q = 1 − pt = Σ_{k≠lab} e_k / Σ_k e_k (no cancellation) and
+// w = wts[lab], a row takes part iff 0 <= lab < K and w > 0 (a weight-0 row present in a dense batch
+// and the same row left out of a sparse one give the same sums):
+//   F   = Σ w·q^γ·(−log pt) / Σ w                                      (γ = 0: the weighted CE above)
+//   I_c = Σ p_c·[lab = c]   P_c = Σ p_c   T_c = Σ [lab = c]            (rows that take part)
+//   D   = 1 − (1/|S|) Σ_{c∈S} (2·I_c + ε) / (P_c + T_c + ε),  S = {c : wts[c] > 0}
+//   loss = ce_weight·F + dice_weight·D     (a term whose weight is 0 is not evaluated: its columns stay 0)
+// fwd: the partial columns of pixel_ce_fwd_kernel (Σ w·q^γ·ce in column 0; counts and hits over every
+//      labelled row, as there), then I_c, P_c, T_c: 4 + 5K columns.
+// bwd: coef_k = g·[ce_weight·w·f/Σw·(p_k − [k = lab]) + dice_weight·p_k·(g_k − Σ_c p_c·g_c)] with
+//      f = q^γ + γ·pt·q^(γ−1)·ce (ce = −log pt; exactly 1 at γ = 0, 0 at q = 0 with γ > 0) and
+//      g_c = a_c·[lab = c] + b_c, a_c = −2/(|S|·U_c), b_c = (2·I_c + ε)/(|S|·U_c²) on S, else 0;
+//      dH, dW | db partials exactly as pixel_ce_bwd_kernel, summed by pixel_ce_wgrad_kernel.
+// γ, the two weights and ε are kernel arguments: constants of a run, baked into a captured graph.
+
+// q^γ on q in [0, 1]: γ = 0 does not touch q, γ = 2 is a multiply, else 2^(γ·log2 q), 0 at q = 0
+__device__ __forceinline__ float focal_pow(float q, float gamma) {
+  if (gamma == 0.f) return 1.f;
+  if (gamma == 2.f) return q * q;
+  return q > 0.f ? fast_exp2(gamma * __log2f(q)) : 0.f;
+}
+
+// f = q^γ − γ·pt·q^(γ−1)·log pt = q^γ·(1 + γ·pt·ce/q): no q^(γ−1), so nothing grows as q → 0
+__device__ __forceinline__ float focal_factor(float q, float pt, float ce, float gamma) {
+  if (gamma == 0.f) return 1.f;
+  if (gamma == 2.f) return q * (q + 2.f * pt * ce);
+  return q > 0.f ? focal_pow(q, gamma) * (1.f + gamma * pt * ce / q) : 0.f;
+}
+
+template <int C, int K>
+__global__ __launch_bounds__(256) void pixel_seg_fwd_kernel(const float* __restrict__ H, const float* __restrict__ W,
+                                                            const float* __restrict__ bias,
+                                                            const int64_t* __restrict__ labels,
+                                                            const float* __restrict__ wts, float gamma, float cew,
+                                                            float dcw, long long R, float* __restrict__ part) {
+  constexpr int CPL = C / 16, NS = 4 + 5 * K, OI = 4 + 2 * K, OP = OI + K, OT = OP + K;
+  const int l = lane_id(), w = wave_id(), sub = l & 15, grp = l >> 4;
+  float wk[K][CPL], bk[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    load_row<CPL>(W + k * C + sub * CPL, wk[k]);
+    bk[k] = bias[k];
+  }
+  float acc[NS];
+#pragma unroll
+  for (int s = 0; s < NS; ++s) acc[s] = 0.f;
+  for (long long r = (long long)blockIdx.x * PH_ROWS + w * 4 + grp; r < R; r += (long long)gridDim.x * PH_ROWS) {
+    float h[CPL], z[K];
+    load_row<CPL>(H + r * C + sub * CPL, h);
+    const long long lab64 = labels[r];
+    row_logits<C, K>(h, wk, bk, z);
+    const int lab = (lab64 >= 0 && lab64 < K) ? (int)lab64 : -1;
+    float m = z[0];
+    int pred = 0;
+#pragma unroll
+    for (int k = 1; k < K; ++k) {
+      pred = z[k] > m ? k : pred;
+      m = fmaxf(m, z[k]);
+    }
+    float e[K], se = 0.f, zl = 0.f, eo = 0.f, wl = 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      e[k] = __expf(z[k] - m);
+      se += e[k];
+      zl = k == lab ? z[k] : zl;
+      eo += k == lab ? 0.f : e[k];
+    }
+    if (lab >= 0) wl = wts[lab];
+    if (sub == 0 && lab >= 0) {
+      const float hit = pred == lab ? 1.f : 0.f;
+      if (lab > 0) {
+        acc[2] += 1.f;
+        acc[3] += hit;
+      }
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        acc[4 + 2 * k] += k == lab ? 1.f : 0.f;
+        acc[5 + 2 * k] += k == lab ? hit : 0.f;
+      }
+      if (wl > 0.f) {
+        acc[1] += wl;
+        const float inv = 1.f / se;
+        if (cew > 0.f) {
+          const float ce = m + __logf(se) - zl;
+          acc[0] += wl * focal_pow(eo * inv, gamma) * ce;
+        }
+        if (dcw > 0.f) {
+#pragma unroll
+          for (int k = 0; k < K; ++k) {
+            const float p = e[k] * inv;
+            acc[OI + k] += k == lab ? p : 0.f;
+            acc[OP + k] += p;
+            acc[OT + k] += k == lab ? 1.f : 0.f;
+          }
+        }
+      }
+    }
+  }
+  __shared__ float sred[4][NS];
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    const float v = wave_sum(acc[s]);
+    if (l == 0) sred[w][s] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < NS)
+    part[(long long)blockIdx.x * NS + threadIdx.x] =
+        sred[0][threadIdx.x] + sred[1][threadIdx.x] + sred[2][threadIdx.x] + sred[3][threadIdx.x];
+}
+
+// stats = [column sums of the partials (NS = 4 + 5K) | acc(lab > 0), acc_1 … acc_{K-1} | F, D |
+// (2·I_c + ε)/U_c for every class c], loss = ce_weight·F + dice_weight·D; a term whose weight is 0
+// reads 0 (so do its per-class coefficients).  One block of 16 waves: wave w sums the columns w and
+// w + 16 in the order of pixel_ce_finalize_kernel (up to 24 columns do not fit one wave each).
+__global__ __launch_bounds__(1024) void pixel_seg_finalize_kernel(const float* __restrict__ part, int nblk, int K,
+                                                                 const float* __restrict__ wts, float cew, float dcw,
+                                                                 float eps, float* __restrict__ stats,
+                                                                 float* __restrict__ loss) {
+  const int w = wave_id(), l = lane_id(), NS = 4 + 5 * K;
+  __shared__ float tot[24];  // NS <= 24 (K <= 4)
+  for (int c = w; c < NS; c += 16) {
+    float s = 0.f;
+    for (int i = l; i < nblk; i += 64) s += part[(long long)i * NS + c];
+    s = wave_sum(s);
+    if (l == 0) tot[c] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int j = 0; j < NS; ++j) stats[j] = tot[j];
+    stats[NS] = tot[2] > 0.f ? tot[3] / tot[2] : 0.f;
+    for (int k = 1; k < K; ++k) stats[NS + k] = tot[4 + 2 * k] > 0.f ? tot[5 + 2 * k] / tot[4 + 2 * k] : 0.f;
+    const float F = cew > 0.f ? tot[0] / tot[1] : 0.f;
+    float D = 0.f;
+    if (dcw > 0.f) {
+      float ns = 0.f, ds = 0.f;
+      for (int c = 0; c < K; ++c) {
+        const float d = (2.f * tot[4 + 2 * K + c] + eps) / (tot[4 + 3 * K + c] + tot[4 + 4 * K + c] + eps);
+        stats[NS + K + 2 + c] = d;
+        if (wts[c] > 0.f) {
+          ns += 1.f;
+          ds += d;
+        }
+      }
+      D = 1.f - ds / ns;
+    } else {
+      for (int c = 0; c < K; ++c) stats[NS + K + 2 + c] = 0.f;
+    }
+    stats[NS + K] = F;
+    stats[NS + K + 1] = D;
+    loss[0] = (cew > 0.f ? cew * F : 0.f) + (dcw > 0.f ? dcw * D : 0.f);
+  }
+}
+
+template <int C, int K>
+__global__ __launch_bounds__(256) void pixel_seg_bwd_kernel(const float* __restrict__ H, const float* __restrict__ W,
+                                                            const float* __restrict__ bias,
+                                                            const int64_t* __restrict__ labels,
+                                                            const float* __restrict__ wts, float gamma, float cew,
+                                                            float dcw, float eps, const float* __restrict__ gout,
+                                                            const float* __restrict__ stats, long long R,
+                                                            float* __restrict__ dH, float* __restrict__ part) {
+  constexpr int CPL = C / 16, NP = K * C + K, OI = 4 + 2 * K, OP = OI + K, OT = OP + K;
+  const int l = lane_id(), w = wave_id(), sub = l & 15, grp = l >> 4;
+  float wk[K][CPL], bk[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    load_row<CPL>(W + k * C + sub * CPL, wk[k]);
+    bk[k] = bias[k];
+  }
+  const float gs = cew > 0.f ? gout[0] * cew / stats[1] : 0.f;  // the focal term's gradient over Σw
+  float ca[K], cb[K];  // g·dice_weight·(a_c, b_c)
+  {
+    float ns = 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) ns += wts[k] > 0.f ? 1.f : 0.f;
+    const float gd = dcw > 0.f ? gout[0] * dcw / ns : 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const float u = stats[OP + k] + stats[OT + k] + eps;
+      const bool in = dcw > 0.f && wts[k] > 0.f;
+      ca[k] = in ? -2.f * gd / u : 0.f;
+      cb[k] = in ? gd * (2.f * stats[OI + k] + eps) / (u * u) : 0.f;
+    }
+  }
+  float gw[K][CPL], gb[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    gb[k] = 0.f;
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) gw[k][j] = 0.f;
+  }
+  for (long long r = (long long)blockIdx.x * PH_ROWS + w * 4 + grp; r < R; r += (long long)gridDim.x * PH_ROWS) {
+    float h[CPL], z[K];
+    load_row<CPL>(H + r * C + sub * CPL, h);
+    const long long lab64 = labels[r];
+    row_logits<C, K>(h, wk, bk, z);
+    const int lab = (lab64 >= 0 && lab64 < K) ? (int)lab64 : -1;
+    float m = z[0];
+#pragma unroll
+    for (int k = 1; k < K; ++k) m = fmaxf(m, z[k]);
+    float se = 0.f, zl = 0.f, el = 0.f, eo = 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      zl = k == lab ? z[k] : zl;
+      z[k] = __expf(z[k] - m);
+      se += z[k];
+      el = k == lab ? z[k] : el;
+      eo += k == lab ? 0.f : z[k];
+    }
+    const float wl = lab >= 0 ? wts[lab] : 0.f;
+    const bool take = wl > 0.f;
+    const float inv = 1.f / se;
+    float coef[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      z[k] *= inv;  // softmax
+      coef[k] = 0.f;
+    }
+    if (cew > 0.f) {
+      float f = 1.f;
+      if (gamma != 0.f) f = focal_factor(eo * inv, el * inv, m + __logf(se) - zl, gamma);
+      const float fs = take ? wl * gs * f : 0.f;
+#pragma unroll
+      for (int k = 0; k < K; ++k) coef[k] = fs * (z[k] - (k == lab ? 1.f : 0.f));
+    }
+    if (dcw > 0.f) {
+      float g[K], s = 0.f;
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        g[k] = cb[k] + (k == lab ? ca[k] : 0.f);
+        s = fmaf(z[k], g[k], s);
+      }
+#pragma unroll
+      for (int k = 0; k < K; ++k) coef[k] += take ? z[k] * (g[k] - s) : 0.f;
+    }
+    float dh[CPL];
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) {
+      float s = 0.f;
+#pragma unroll
+      for (int k = 0; k < K; ++k) s = fmaf(coef[k], wk[k][j], s);
+      dh[j] = s;
+    }
+    float* dp = dH + r * C + sub * CPL;
+    if constexpr (CPL % 4 == 0) {
+#pragma unroll
+      for (int j = 0; j < CPL; j += 4) *reinterpret_cast<float4*>(dp + j) = make_float4(dh[j], dh[j + 1], dh[j + 2], dh[j + 3]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < CPL; j += 2) *reinterpret_cast<float2*>(dp + j) = make_float2(dh[j], dh[j + 1]);
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+#pragma unroll
+      for (int j = 0; j < CPL; ++j) gw[k][j] = fmaf(coef[k], h[j], gw[k][j]);
+      gb[k] += sub == 0 ? coef[k] : 0.f;
+    }
+  }
+  // the 4 row groups of a wave hold the same channels (lanes l, l ^ 16, l ^ 32, l ^ 48)
+  __shared__ float sred[4][NP];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) {
+      const float v = xor32_sum(xor16_sum(gw[k][j]));
+      if (grp == 0) sred[w][k * C + sub * CPL + j] = v;
+    }
+    const float vb = wave_sum(gb[k]);
+    if (l == 0) sred[w][K * C + k] = vb;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < NP; i += blockDim.x)
+    part[(long long)blockIdx.x * NP + i] = sred[0][i] + sred[1][i] + sred[2][i] + sred[3][i];
+}
+
+// part: (pixel_ce_blocks(R), 4 + 5K), zero-filled by the caller when R == 0 (no row launch then);
+// stats: 6 + 7K floats (layout above pixel_seg_finalize_kernel)
+void pixel_seg_fwd_launch(int C, int K, const float* H, const float* W, const float* bias, const int64_t* labels,
+                          const float* wts, float gamma, float ce_weight, float dice_weight, float eps, long long R,
+                          float* part, float* stats, float* loss, hipStream_t st) {
+  if (R > 0) PH_DISPATCH(pixel_seg_fwd_kernel, H, W, bias, labels, wts, gamma, ce_weight, dice_weight, R, part);
+  hipLaunchKernelGGL(pixel_seg_finalize_kernel, dim3(1), dim3(1024), 0, st, part, pixel_ce_blocks(R), K, wts, ce_weight,
+                     dice_weight, eps, stats, loss);
+}
+
+// part: (pixel_ce_blocks(R), K·C + K), zero-filled by the caller when R == 0; dW / db accumulated
+void pixel_seg_bwd_launch(int C, int K, const float* H, const float* W, const float* bias, const int64_t* labels,
+                          const float* wts, float gamma, float ce_weight, float dice_weight, float eps,
+                          const float* gout, const float* stats, long long R, float* dH, float* part, float* dW,
+                          float* db, hipStream_t st) {
+  if (R > 0)
+    PH_DISPATCH(pixel_seg_bwd_kernel, H, W, bias, labels, wts, gamma, ce_weight, dice_weight, eps, gout, stats, R, dH,
+                part);
+  const int NP = K * C + K;
+  hipLaunchKernelGGL(pixel_ce_wgrad_kernel, dim3((NP + 63) / 64), dim3(1024), 0, st, part, pixel_ce_blocks(R), NP,
+                     K * C, dW, db);
+}
 #undef PH_DISPATCH
 
 // ---- nonzero_compact: dense image (B, npix) → the sparse operands of the encoder ----------------

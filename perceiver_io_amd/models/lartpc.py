@@ -42,6 +42,16 @@ NUM_CLASSES = 3
 CLASS_WEIGHTS = (0.0, 1.0, 1.0)  # background, track, shower (reference run.py:238-240)
 
 
+class SegLoss(NamedTuple):
+    """The segmentation loss of :func:`ops.pixel_head.pixel_seg_loss`: ``ce_weight`` · focal
+    cross-entropy (``focal_gamma`` = 0: the weighted cross-entropy) + ``dice_weight`` · soft Dice."""
+
+    focal_gamma: float = 0.0
+    ce_weight: float = 1.0
+    dice_weight: float = 0.0
+    dice_eps: float = 1.0
+
+
 class Segmentation(NamedTuple):
     """Result of :meth:`LArPerceiver.segment` / :meth:`LArPerceiver.segment_sparse`."""
 
@@ -115,19 +125,26 @@ class LArPerceiver(torch.nn.Module):
         """Logits ``(B, K', 3)`` at output pixels ``qidx`` from the non-zero pixels only."""
         return self.perceiver.decoder.output_adapter.linear(self.sparse_hidden(values, index, kmask, qidx))
 
-    def sparse_loss(self, batch, weights: torch.Tensor) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
+    def sparse_loss(self, batch, weights: torch.Tensor,
+                    loss: Optional[SegLoss] = None) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
         """``(loss, {acc, acc1, acc2})`` for a :func:`data.lartpc.sparse_collate` batch: the
         weighted mean cross-entropy of the dense model (ignored slots are -100) and the
         reference's per-class accuracies, as device tensors.  On the GPU the 3-way head, the
-        loss and the accuracies are one fused kernel each way (``ops/pixel_head.py``)."""
-        from ..ops.pixel_head import pixel_ce
+        loss and the accuracies are one fused kernel each way (``ops/pixel_head.py``).
+
+        ``loss`` (a :class:`SegLoss`) selects focal cross-entropy + soft Dice instead
+        (``pixel_seg_loss``; the metrics gain ``focal``, ``dice``, ``dice1``, ``dice2``).  Only pixels
+        with a positive class weight take part in it, so it too equals its dense computation."""
+        from ..ops.pixel_head import pixel_ce, pixel_seg_loss
 
         values, index, kmask, qidx, qlab = batch
         h = self.sparse_hidden(values, index, kmask, qidx)
-        return pixel_ce(h, self.perceiver.decoder.output_adapter.linear, qlab, weights)
+        if loss is None:
+            return pixel_ce(h, self.perceiver.decoder.output_adapter.linear, qlab, weights)
+        return pixel_seg_loss(h, self.perceiver.decoder.output_adapter.linear, qlab, weights, *loss)
 
     def event_loss(self, batch, weights: torch.Tensor, key_capacity: int, query_capacity: int,
-                   class_weights: Sequence[float] = CLASS_WEIGHTS):
+                   class_weights: Sequence[float] = CLASS_WEIGHTS, loss: Optional[SegLoss] = None):
         """``(loss, {acc, acc1, acc2}, counts)`` for dense events ``batch = (img (B, H, W) fp32, lab
         (B, H·W) uint8, words (B,) int32)``: ``ops.event_compact`` builds the sparse batch on the
         batch's device, each sample under the dihedral code in ``words``, and :meth:`sparse_loss`
@@ -135,13 +152,13 @@ class LArPerceiver(torch.nn.Module):
         queries is decided without reading the device).  Shapes depend on the capacities alone, so
         one captured graph serves every batch.  Pixels past a capacity are left out of the loss, as
         in ``segment(capacity=)``; ``counts`` (B, 2) int32 holds the true key and query counts, so
-        the caller can see that."""
+        the caller can see that.  ``loss``: as in :meth:`sparse_loss`."""
         from .. import ops
 
         img, lab, words = batch
         *sparse, counts = ops.event_compact(img, lab, words, int(key_capacity), int(query_capacity), class_weights)
-        loss, acc = self.sparse_loss(tuple(sparse), weights)
-        return loss, acc, counts
+        value, acc = self.sparse_loss(tuple(sparse), weights, loss)
+        return value, acc, counts
 
     def segment_sparse(self, values, index, kmask, qidx=None, qmask=None, labels=None) -> Segmentation:
         """Class map of a sparse batch (``sparse_collate`` layout, or :func:`nonzero_compact`'s).

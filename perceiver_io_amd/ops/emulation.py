@@ -1292,6 +1292,111 @@ def pixel_ce_bwd(h, w, b, labels, wts, gout, stats, dH, dW, db):
     db += coef.sum(0)
 
 
+def check_seg_params(gamma, ce_weight, dice_weight, eps):
+    """The parameter rules of the segmentation loss (the host checks of ``pixel_seg_fwd``)."""
+    import math
+
+    vals = (gamma, ce_weight, dice_weight, eps)
+    if not all(isinstance(v, (int, float)) and math.isfinite(v) for v in vals):
+        raise ValueError(f"pixel seg: finite numbers expected, got {vals}")
+    if gamma < 0:
+        raise ValueError(f"pixel seg: focal gamma must be >= 0, got {gamma}")
+    if ce_weight < 0 or dice_weight < 0 or ce_weight + dice_weight <= 0:
+        raise ValueError(f"pixel seg: ce_weight and dice_weight must be >= 0 and not both 0, got {ce_weight}, {dice_weight}")
+    if eps <= 0:
+        raise ValueError(f"pixel seg: dice eps must be > 0, got {eps}")
+
+
+def _pixel_seg_rows(h, w, b, labels, wts):
+    """Per row: softmax p, one-hot label, ce = −log p[lab], q = Σ_{k≠lab} p_k, the label's weight and
+    whether the row takes part (0 <= lab < K and weight > 0)."""
+    K = w.shape[0]
+    z = _pixel_logits(h, w, b)
+    valid = (labels >= 0) & (labels < K)
+    lab = labels.clamp(0, K - 1)
+    oh = torch.nn.functional.one_hot(lab, K).float()
+    p = torch.softmax(z, -1)
+    ce = torch.logsumexp(z, -1) - z.gather(1, lab[:, None])[:, 0]
+    q = (p * (1 - oh)).sum(-1)
+    wl = torch.where(valid, wts.float()[lab], torch.zeros_like(ce))
+    return p, oh, ce, q, wl, valid & (wl > 0)
+
+
+def _focal_pow(q, gamma):
+    """q^γ: γ = 0 does not touch q; 0 at q = 0 for γ > 0."""
+    if gamma == 0:
+        return torch.ones_like(q)
+    if gamma == 2:
+        return q * q
+    return torch.where(q > 0, torch.exp2(gamma * torch.log2(q.clamp(min=torch.finfo(q.dtype).tiny))), torch.zeros_like(q))
+
+
+def pixel_seg_fwd(h, w, b, labels, wts, gamma, ce_weight, dice_weight, eps):
+    """(stats, loss) of pixel_head.hip ``pixel_seg_fwd``: stats = [the 4 + 2K sums of ``pixel_ce_fwd``
+    with Σ w·q^γ·ce first, I_c, P_c, T_c | acc, acc_1 … | F, D | (2·I_c + ε)/U_c per class],
+    loss = ce_weight·F + dice_weight·D.  A term whose weight is 0 is not evaluated and reads 0."""
+    check_seg_params(gamma, ce_weight, dice_weight, eps)
+    K = w.shape[0]
+    base = _pixel_ce_sums(h, w, b, labels, wts)
+    p, oh, ce, q, wl, take = _pixel_seg_rows(h, w, b, labels, wts)
+    zero = torch.zeros_like(ce)
+    fsum = torch.where(take, wl * _focal_pow(q, gamma) * ce, zero).sum() if ce_weight > 0 else zero.sum()
+    if dice_weight > 0:
+        pm, om = p * take[:, None], oh * take[:, None]
+        ipt = torch.cat([(pm * om).sum(0), pm.sum(0), om.sum(0)])
+    else:
+        ipt = torch.zeros(3 * K, device=h.device)
+    part = torch.cat([fsum[None], base[1:], ipt])
+
+    def ratio(hit, n):
+        return torch.where(n > 0, hit / n.clamp(min=1), torch.zeros_like(n))
+
+    accs = [ratio(part[3], part[2])] + [ratio(part[5 + 2 * k], part[4 + 2 * k]) for k in range(1, K)]
+    F = part[0] / part[1] if ce_weight > 0 else zero.sum()
+    if dice_weight > 0:
+        I, P, T = ipt[:K], ipt[K:2 * K], ipt[2 * K:]
+        dice = (2 * I + eps) / (P + T + eps)
+        S = (wts > 0).float()
+        D = 1 - (dice * S).sum() / S.sum()
+    else:
+        dice, D = torch.zeros(K, device=h.device), zero.sum()
+    loss = (ce_weight * F if ce_weight > 0 else 0) + (dice_weight * D if dice_weight > 0 else 0)
+    return torch.cat([part, torch.stack(accs), torch.stack([F, D]), dice]), loss
+
+
+def pixel_seg_bwd(h, w, b, labels, wts, gamma, ce_weight, dice_weight, eps, gout, stats, dH, dW, db):
+    """The closed-form gradient of ``pixel_seg_fwd`` (pixel_head.hip ``pixel_seg_bwd_kernel``): dH
+    written, dW / db accumulated; ``stats`` is the forward's."""
+    check_seg_params(gamma, ce_weight, dice_weight, eps)
+    K = w.shape[0]
+    g = gout.reshape(1).float()
+    p, oh, ce, q, wl, take = _pixel_seg_rows(h, w, b, labels, wts)
+    coef = torch.zeros_like(p)
+    if ce_weight > 0:
+        pt = (p * oh).sum(-1)
+        if gamma == 0:
+            f = torch.ones_like(q)
+        elif gamma == 2:
+            f = q * (q + 2 * pt * ce)
+        else:  # q^γ·(1 + γ·pt·ce/q) = q^γ − γ·pt·q^(γ−1)·log pt, 0 at q = 0
+            tiny = torch.finfo(q.dtype).tiny
+            f = torch.where(q > 0, _focal_pow(q, gamma) * (1 + gamma * pt * ce / q.clamp(min=tiny)), torch.zeros_like(q))
+        coef = coef + (wl * f * (g * ce_weight / stats[1]))[:, None] * (p - oh)
+    if dice_weight > 0:
+        I, P, T = stats[4 + 2 * K:4 + 3 * K], stats[4 + 3 * K:4 + 4 * K], stats[4 + 4 * K:4 + 5 * K]
+        S = wts > 0
+        U = P + T + eps
+        gd = g * dice_weight / S.sum()
+        a = torch.where(S, -2 * gd / U, torch.zeros_like(U))
+        bb = torch.where(S, gd * (2 * I + eps) / (U * U), torch.zeros_like(U))
+        gk = oh * a + bb
+        coef = coef + p * (gk - (p * gk).sum(-1, keepdim=True))
+    coef = torch.where(take[:, None], coef, torch.zeros_like(coef))
+    dH.copy_(coef @ w.float())
+    dW += (coef.t() @ h.float()).view_as(dW)
+    db += coef.sum(0)
+
+
 def pixel_predict(h, w, b, qidx, qvalid, Q, npix, labels=None):
     """[classes (R) uint8, conf (R) fp32, class_map (R / Q, npix) uint8 (+ confusion partials
     (1, K·K) int32 with labels)] of pixel_head.hip ``pixel_predict_kernel``: argmax with the lowest

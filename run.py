@@ -29,6 +29,13 @@ on the host and the compaction reads the pixels through it (validation runs code
 ``--key-capacity`` / ``--query-capacity`` are sized by one counting pass over both loaders.  Pixels
 past a capacity are dropped from the loss, and every log step that sees an overflow says so.
 
+``--focal-gamma G``, ``--dice-weight D``, ``--ce-weight W`` and ``--dice-eps E`` replace the weighted
+cross-entropy by ``W`` · focal cross-entropy (γ = ``G``) + ``D`` · soft Dice, the two usual losses for
+data this unbalanced (``ops.pixel_head.pixel_seg_loss``).  Training and validation use it on every
+path: the fused head kernels on the sparse ones, an eager composition of the same definition with
+``--dense``.  The two component values and the per-class Dice coefficients are logged beside the
+accuracies.  With none of the four given, nothing changes.
+
 ``--engine eager`` (the default on CPU) runs the reference sequence exactly: zero_grad,
 forward, ``scheduler.step(loss)``, backward, ``clip_grad_norm_``, ``Adam.step``.
 
@@ -40,6 +47,7 @@ parameters.  The unused U-ResNet never has a gradient, and torch's Adam skips it
 
     python run.py [--epochs 10] [--events 64] [--size 512] [--batch-size 4] [--dense] [--engine eager]
     python run.py --device-collate --augment dihedral [--key-capacity K] [--query-capacity Q]
+    python run.py --focal-gamma 2 --dice-weight 0.5 [--ce-weight 1] [--dice-eps 1]
 
 ``--segment CKPT --out DIR`` trains nothing: it loads ``model_state_dict`` from the checkpoint,
 segments the validation events through ``LArPerceiver.segment`` (sparse, no dense logits) and
@@ -62,7 +70,9 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from perceiver_io_amd.data.lartpc import DenseCollator, DihedralAugment, SparseCollator, _round_up  # noqa: E402
 from perceiver_io_amd.data.synthetic import SyntheticLArTPC  # noqa: E402
-from perceiver_io_amd.models.lartpc import LArPerceiver, accuracies, class_weights, iou  # noqa: E402
+from perceiver_io_amd.models.lartpc import LArPerceiver, SegLoss, accuracies, class_weights, iou  # noqa: E402
+from perceiver_io_amd.ops.emulation import check_seg_params  # noqa: E402
+from perceiver_io_amd.ops.pixel_head import seg_loss_logits  # noqa: E402
 from perceiver_io_amd.train.loggers import TensorBoardLogger  # noqa: E402
 
 __all__ = ["LArPerceiver", "accuracies", "main"]
@@ -72,29 +82,35 @@ def _to(batch, dev):
     return tuple(t.to(dev, non_blocking=True) for t in batch)
 
 
-def make_step_fn(model, weights, sparse: bool, metrics: dict):
-    """loss_fn(batch) → loss; per-class accuracies of the batch land in ``metrics`` (device)."""
+def make_step_fn(model, weights, sparse: bool, metrics: dict, seg=None):
+    """loss_fn(batch) → loss; per-class accuracies of the batch land in ``metrics`` (device).  With
+    ``seg`` (a ``SegLoss``) the loss is focal cross-entropy + soft Dice, and its two component
+    values and the per-class Dice coefficients land there too."""
 
     def loss_fn(batch):
         if sparse:
-            loss, acc = model.sparse_loss(batch, weights)
+            loss, acc = model.sparse_loss(batch, weights, seg)
         else:
             img, lab = batch
             out = model(img)
-            loss = F.cross_entropy(out, lab, weight=weights)
-            acc = accuracies(out.argmax(1).detach(), lab)
+            if seg is None:
+                loss = F.cross_entropy(out, lab, weight=weights)
+                acc = accuracies(out.argmax(1).detach(), lab)
+            else:  # logits exist here: the same definition as an eager composition
+                loss, acc = seg_loss_logits(out.permute(0, 2, 1), lab, weights, *seg)
         metrics.update(acc)
         return loss
 
     return loss_fn
 
 
-def make_event_step_fn(model, weights, caps, metrics: dict, side: dict):
+def make_event_step_fn(model, weights, caps, metrics: dict, side: dict, seg=None):
     """loss_fn((img, lab, words)) → loss of ``--device-collate``; accuracies land in ``metrics``, the
-    batch's true key / query counts (B, 2) in ``side`` (device tensors)."""
+    batch's true key / query counts (B, 2) in ``side`` (device tensors).  ``seg``: as in
+    :func:`make_step_fn`."""
 
     def loss_fn(batch):
-        loss, acc, counts = model.event_loss(batch, weights, caps[0], caps[1])
+        loss, acc, counts = model.event_loss(batch, weights, caps[0], caps[1], loss=seg)
         metrics.update(acc)
         side["counts"] = counts
         return loss
@@ -177,6 +193,10 @@ def parse_args(argv=None):
     ap.add_argument("--key-capacity", type=int, default=None, help="key slots per event (default: counted, rounded to --bucket)")
     ap.add_argument("--query-capacity", type=int, default=None, help="query slots per event (default: counted)")
     ap.add_argument("--seed", type=int, default=0, help="seed of the augmentation draws")
+    ap.add_argument("--focal-gamma", type=float, default=None, help="focal exponent of the cross-entropy term (default 0)")
+    ap.add_argument("--ce-weight", type=float, default=None, help="weight of the (focal) cross-entropy term (default 1)")
+    ap.add_argument("--dice-weight", type=float, default=None, help="weight of the soft-Dice term (default 0)")
+    ap.add_argument("--dice-eps", type=float, default=None, help="smoothing of the soft-Dice coefficients (default 1)")
     ap.add_argument("--segment", metavar="CKPT", default=None,
                     help="no training: segment the validation events with this checkpoint and write class maps to --out")
     ap.add_argument("--out", metavar="DIR", default="segmented", help="output directory of --segment")
@@ -185,6 +205,14 @@ def parse_args(argv=None):
         ap.error("--augment needs --device-collate")
     if a.device_collate and a.dense:
         ap.error("--device-collate builds sparse batches: drop --dense")
+    given = (a.focal_gamma, a.ce_weight, a.dice_weight, a.dice_eps)
+    a.seg_loss = None  # none of the four given: the weighted cross-entropy, exactly as before
+    if any(v is not None for v in given):
+        a.seg_loss = SegLoss(*(d if v is None else v for v, d in zip(given, SegLoss())))
+        try:
+            check_seg_params(*a.seg_loss)
+        except ValueError as e:
+            ap.error(str(e))
     return a
 
 
@@ -228,9 +256,11 @@ def main(argv=None):
             caps = tuple(c if c is not None else n for c, n in zip(caps, counted))
         print(f"device collate: {caps[0]} key and {caps[1]} query slots per event, augment {a.augment}", flush=True)
         aug, rng = DihedralAugment(a.augment), DihedralAugment.rng(a.seed, 0)
-        loss_fn = make_event_step_fn(model, weights, caps, metrics, side)
+        loss_fn = make_event_step_fn(model, weights, caps, metrics, side, a.seg_loss)
     else:
-        loss_fn = make_step_fn(model, weights, sparse, metrics)
+        loss_fn = make_step_fn(model, weights, sparse, metrics, a.seg_loss)
+    if a.seg_loss is not None:
+        print("loss: {1:g} x focal CE (gamma {0:g}) + {2:g} x soft Dice (eps {3:g})".format(*a.seg_loss), flush=True)
 
     def with_words(batch, training: bool):
         if aug is None:
@@ -272,7 +302,8 @@ def main(argv=None):
                 vals = {k: float(v) for k, v in metrics.items()}
                 log.log_metrics({"loss": float(loss), "lr": opt.param_groups[0]["lr"],
                                  **{f"train_{k}": v for k, v in vals.items()}}, step)
-                print(f"epoch {epoch} step {step} loss {float(loss):.4f} acc {vals.get('acc', 0):.3f} "
+                parts = "".join(f" {k} {vals[k]:.4f}" for k in ("focal", "dice") if k in vals)
+                print(f"epoch {epoch} step {step} loss {float(loss):.4f}{parts} acc {vals.get('acc', 0):.3f} "
                       f"{time.perf_counter() - t0:.3f}s", flush=True)
                 if caps is not None:
                     report_overflow(side["counts"], caps, step)
@@ -280,18 +311,22 @@ def main(argv=None):
             if 0 < a.max_steps <= step:
                 break
         model.eval()
-        vl, va = [], []
+        vl, va, vs = [], [], {}
         with torch.no_grad():
             for batch in val:
                 batch = _to(with_words(batch, False), dev)
                 vm: dict = {}
                 if caps is not None:
-                    vl.append(float(make_event_step_fn(model, weights, caps, vm, {})(batch)))
+                    vl.append(float(make_event_step_fn(model, weights, caps, vm, {}, a.seg_loss)(batch)))
                 else:
-                    vl.append(float(make_step_fn(model, weights, sparse, vm)(batch)))
+                    vl.append(float(make_step_fn(model, weights, sparse, vm, a.seg_loss)(batch)))
                 va.append(float(vm["acc"]))
+                for k, v in vm.items():  # the new loss's components and per-class Dice
+                    if k == "focal" or k.startswith("dice"):
+                        vs.setdefault(k, []).append(float(v))
         if vl:
-            log.log_metrics({"validation_loss": sum(vl) / len(vl), "val_acc": sum(va) / len(va)}, step)
+            log.log_metrics({"validation_loss": sum(vl) / len(vl), "val_acc": sum(va) / len(va),
+                             **{f"val_{k}": sum(v) / len(v) for k, v in vs.items()}}, step)
             print(f"validation loss: {sum(vl) / len(vl):.4f}", flush=True)
         if 0 < a.max_steps <= step:
             break
