@@ -432,7 +432,9 @@ __global__ __launch_bounds__(256) void ce_bwd_dw_reg_kernel(const uint16_t* __re
   auto fetch = [&](int mt) {
     fetch_rows<C>(hr, Hm, mt * HB, M);
     const int t = threadIdx.x & 63, gr = mt * HB + t;
-    if (threadIdx.x < 64) aux = gr < M ? lse[gr] * kL2E : 0.f;
+    // a row past M: +inf, so p = 2^−inf = 0 (against 0 a bias above 88 gave p = inf, and inf·0 = NaN
+    // in every dW / db entry of the vocabulary block)
+    if (threadIdx.x < 64) aux = gr < M ? lse[gr] * kL2E : __builtin_inff();
     else if (threadIdx.x < 128) aux = __int_as_float(gr < M ? (int)labels[gr] : -100);
   };
   if (mt_begin < mt_end) fetch(mt_begin);
